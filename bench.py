@@ -5,7 +5,11 @@ Output: stdout carries ONE compact JSON line (< 6 KB: headline + `roofline` + `c
 record per side leg); the full result of every leg goes to `bench_full.json` beside this script (also `gpurun_out/`) and to
 stderr.  `compact_line()` builds the line; tests/test_bench_line.py holds its size.
 
-`python bench.py --gpus N --steps K --warmup W`.  With N > 1 and no WORLD_SIZE in the environment the script launches
+`python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`.  A plain run is the headline alone: set-up, the
+warm-up, the K timed steps of the main line (exactly K: `ms_per_step` = their wall time / K) and the line.  `--dump-outputs DIR`
+writes the metric values of the last timed step as DIR/<name>.npy (float64; the inputs are seeded, so two builds compare output
+for output).  `--full` adds everything else below: the side legs, the CPU baseline, the main line's oracle check and the clock
+probe (`--legs` picks among them).  With N > 1 and no WORLD_SIZE in the environment the script launches
 itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU,
 backend 'nccl' = RCCL); under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE.  Fewer visible devices than N: one JSON
 line with "skipped" and exit code 0.
@@ -26,7 +30,7 @@ value    = (grid points per step x 4 metrics x N) / wall time per step (max over
 roofline = algorithmic bytes (208 B/point: 51 members + the target, read once) / mean duration of the ensemble kernel
            (HIP events on the launch stream, separate pass), against 8.0 TB/s
 
-Side legs in the same line (N = 1 unless noted):
+Side legs, with --full (N = 1 unless noted):
   configs1       BASELINE.json configs[1]: RMSE / MSE / MAE / bias / ACC / activity on f32[40 init, 10 lead, 5 level, 721, 1440]
                  p, t + (dayofyear, hour) climatology (the main line of rounds 1-2)
   ensemble       configs[2]: 6 variables x f32[8, 51, 721, 1440]; `pairwise_form`: the O(M^2) pair kernel alone
@@ -46,7 +50,7 @@ Side legs in the same line (N = 1 unless noted):
   box            the shader clock this box sustains under load (wbx_clock_probe): boxes of the pool differ by 4-8 %
   cpu_baseline   the oracle's "reference structure" NumPy path (one pass per statistic + two einsums, float32
                  statistics; oracle/wbx_oracle.py) on bounded samples: the ensemble suite (the main line's workload) and the
-                 deterministic suite (configs1), each on one process and on os.cpu_count() worker processes
+                 deterministic suite (configs1), each on one process and on usable_cpus() worker processes
                  (oracle/cpu_workers.py); rank 0, N = 1 only.
 """
 import argparse
@@ -84,14 +88,28 @@ def parse():
   ap.add_argument('--pce-mask', choices=['both', '0', '1', 'nan'], default='both',
                   help='public_chunk_ens: run without / with the mask coordinate only (profiling: one kind of launch per traced process)')
   ap.add_argument('--config5-inits', type=int, default=366)
-  ap.add_argument('--cpu-workers', type=int, default=0, help='worker processes of the multi-core CPU baseline (0 = os.cpu_count())')
+  ap.add_argument('--cpu-workers', type=int, default=0,
+                  help='worker processes of the multi-core CPU baseline (0 = the CPUs this process may use, usable_cpus())')
   ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
                   help='torch.distributed backend for N > 1; gloo combines through the host and lets several ranks share '
                        'one device (a plumbing check of the N > 1 path on a 1-GPU box, not a measurement)')
   ap.add_argument('--legs', default='all', help='comma list of main,configs1,ensemble,public_chunk,public_chunk_ens,spectrum,lat_fastest,config5,cpu '
                   '(profiling passes: one kernel shape per trace); default all')
   ap.add_argument('--small', action='store_true', help='tiny sizes (debugging only; not a valid measurement)')
-  return ap.parse_args()
+  ap.add_argument('--full', action='store_true',
+                  help='everything beyond the headline: the side legs, the CPU baseline, the oracle check of the main line and the '
+                       'clock probe (a plain run sets up, warms up, times the K steps of the main line and prints the line)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help="write the metric values of the main line's last timed step to DIR/<name>.npy (float64)")
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
+  side = set() if args.legs == 'all' else set(args.legs.split(',')) - {'main'}
+  if side and not args.full:
+    ap.error(f"--legs {args.legs}: the side legs ({','.join(sorted(side))}) run only with --full")
+  if args.dump_outputs and args.legs != 'all' and 'main' not in args.legs.split(','):
+    ap.error('--dump-outputs writes what the main line computed: --legs must include main')
+  return args
 
 
 def self_launch(args):
@@ -316,7 +334,17 @@ def oracle_level_check(env, ens_level, t_level, got):
   return {'oracle_max_rel_err': max(err.values()), 'oracle_rel_err': err}
 
 
-def main_leg(env):
+def dump_outputs(out, dump_dir):
+  """What the timed path hands its caller -- the metric values of its last step (`<metric>.<variable>`, one value per level) --
+  as DIR/<name>.npy in float64: two builds of the library run on the same seeded inputs compare output for output."""
+  os.makedirs(dump_dir, exist_ok=True)
+  names = sorted(out)
+  for name in names:
+    np.save(os.path.join(dump_dir, f'{name}.npy'), np.asarray(out[name].values, dtype=np.float64))
+  return names
+
+
+def main_leg(env, dump_dir=None):
   """ONE f32[1 init, 37 level, 51 member, lat, lon] forecast per rank against f32[1, 37, lat, lon] targets.
 
   One launch per step, every step on the SAME stream (`--main-streams 1`): a step's kernel then runs alone on the chip, so
@@ -327,12 +355,12 @@ def main_leg(env):
   saved = engine.ALTERNATE_STREAMS
   engine.ALTERNATE_STREAMS = env.args.main_streams == 2
   try:
-    return _main_leg(env)
+    return _main_leg(env, dump_dir)
   finally:
     engine.ALTERNATE_STREAMS = saved
 
 
-def _main_leg(env):
+def _main_leg(env, dump_dir):
   from weatherbenchx_amd import aggregation, distributed, engine, weighting
   from weatherbenchx_amd import xarray_lite as xr
   from weatherbenchx_amd.metrics import base as metrics_base
@@ -405,6 +433,7 @@ def _main_leg(env):
   dt = env.max_over_ranks(time.perf_counter() - t0)
   log = engine.resolve_event_marks([e for e in engine.S1_EVENT_LOG if e['kind'] == 'ens'])
   engine.S1_EVENT_LOG, engine.S1_EVENT_MARKS = None, False
+  dumped = dump_outputs(out, dump_dir) if (dump_dir and env.rank == 0) else None
   ms_per_step = dt / args.steps * 1e3
   points = nlev * env.nlat * env.nlon
   value = points * len(metrics) * env.world / (ms_per_step * 1e-3)
@@ -442,14 +471,17 @@ def _main_leg(env):
                  'collective_backend': env.collective, 'collective': _collective_record(env)},
       'roofline': roofline,
   }
-  # outside the timed region: one sampled level of the timed field against the float64 oracle, every metric of the suite
-  # (the kernel's per-level sums are independent: a level checks the kernel, the planes' addressing and the weights)
+  if dumped is not None:
+    result['outputs'] = {'dir': dump_dir, 'names': dumped, 'step': 'the last timed step'}
+  # outside the timed region (--full): one sampled level of the timed field against the float64 oracle, every metric of the
+  # suite (the kernel's per-level sums are independent: a level checks the kernel, the planes' addressing and the weights)
   crps = float(np.asarray(out['crps.t'].values).mean())
   ssr = float(np.asarray(out['unbiased_spread_skill.t'].values).mean())
   result['check'] = {'crps_mean': crps, 'unbiased_spread_skill_mean': ssr, 'mean_rmse': float(np.asarray(out['mean_rmse.t'].values).mean())}
   if env.world == 1:
-    result['check'].update(oracle_level_check(env, ens[0, nlev // 2], tv[0, nlev // 2],
-                                              {k: np.asarray(out[f'{k}.t'].values).reshape(-1)[nlev // 2] for k in metrics}), level=nlev // 2)
+    if args.full:
+      result['check'].update(oracle_level_check(env, ens[0, nlev // 2], tv[0, nlev // 2],
+                                                {k: np.asarray(out[f'{k}.t'].values).reshape(-1)[nlev // 2] for k in metrics}), level=nlev // 2)
   else:  # (N > 1: the sums combine every rank's field; an exchangeable N(0, 1) ensemble has CRPS ~ 0.5642, spread/skill ~ 1)
     assert np.isfinite(crps) and abs(crps - 0.5642) < 0.01 and abs(ssr - 1.0) < 0.01, (crps, ssr)
   del pe, te, ens, tv
@@ -1283,13 +1315,21 @@ def config5_leg(env, lat_archive=False):
 
 
 # ---- CPU baseline ---------------------------------------------------------------------------------------------------
+def usable_cpus():
+  """The CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the host sets one.  On a shared host
+  os.cpu_count() counts every core of the machine, and one worker process per core would only slow the baseline down."""
+  n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+  cap = os.environ.get('OMP_NUM_THREADS', '')
+  return max(1, min(n, int(cap))) if cap.isdigit() and int(cap) > 0 else max(1, n)
+
+
 def cpu_leg(env, keep):
   """The oracle's reference-structure NumPy path on bounded samples, on this box's host cores: the ensemble suite of the main
   line first (top-level `value`), the deterministic suite of configs1 beside it; each on one process and on all cores."""
   from oracle import cpu_workers
   from oracle import wbx_oracle as O
   args = env.args
-  nworkers = args.cpu_workers or (os.cpu_count() or 1)
+  nworkers = args.cpu_workers or usable_cpus()
   w = O.grid_area_weights(env.lat)
   out = {}
 
@@ -1515,8 +1555,9 @@ def main():
   want = lambda name: legs is None or name in legs
   result, keep = {'metric': METRIC, 'value': None, 'note': 'main leg not selected (--legs)'}, None
   if want('main'):
-    result = main_leg(env)
-  if not args.no_ens and env.world == 1:
+    result = main_leg(env, dump_dir=args.dump_outputs)
+  # everything beyond the headline runs with --full only: a plain run is set-up, warm-up, the K timed steps and the line
+  if args.full and not args.no_ens and env.world == 1:
     if want('configs1'):
       result['configs1'], keep = configs1_leg(env)
     if want('ensemble'):
@@ -1555,16 +1596,17 @@ def main():
       if not args.no_config5 and want('config5'):
         lf['config5'] = config5_leg(env, lat_archive=True)
       result['lat_fastest'] = lf
-  if not args.no_config5 and want('config5'):
+  if args.full and not args.no_config5 and want('config5'):
     result['config5'] = config5_leg(env)
-  if not args.no_cpu and env.world == 1 and env.rank == 0 and want('cpu'):
+  if args.full and not args.no_cpu and env.world == 1 and env.rank == 0 and want('cpu'):
     result['cpu_baseline'] = cpu_leg(env, keep)
   if env.rank == 0:
-    try:  # the clock this box sustains under load, beside the numbers it shaped (boxes of the pool differ by 4-8 %)
-      result['box'] = {'shader_MHz_all_CUs_busy': round(env.ctx.clock_probe(2048), 1), 'shader_MHz_one_block': round(env.ctx.clock_probe(1), 1),
-                       'host_cpus': os.cpu_count()}
-    except Exception as e:  # pylint: disable=broad-except
-      result['box'] = {'error': f'{type(e).__name__}: {e}'}
+    if args.full:
+      try:  # the clock this box sustains under load, beside the numbers it shaped (boxes of the pool differ by 4-8 %)
+        result['box'] = {'shader_MHz_all_CUs_busy': round(env.ctx.clock_probe(2048), 1), 'shader_MHz_one_block': round(env.ctx.clock_probe(1), 1),
+                         'host_cpus': os.cpu_count()}
+      except Exception as e:  # pylint: disable=broad-except
+        result['box'] = {'error': f'{type(e).__name__}: {e}'}
     _emit(result)
   if env.world > 1:
     env.dist.destroy_process_group()

@@ -81,8 +81,8 @@ def test_skipped_line_is_one_small_json_line():
 
 @pytest.mark.gpu
 def test_small_bench_prints_one_parsable_line():
-  proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--small', '--steps', '2', '--warmup', '1', '--prewarm-ms', '0',
-                         '--cpu-workers', '2'], capture_output=True, text=True, timeout=900)
+  proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--small', '--steps', '2', '--warmup', '1', '--prewarm-ms',
+                         '0', '--cpu-workers', '2'], capture_output=True, text=True, timeout=900)
   assert proc.returncode == 0, proc.stderr[-4000:]
   lines = [l for l in proc.stdout.splitlines() if l.strip()]
   assert len(lines) == 1 and len(lines[0]) < 8192, (len(lines), len(lines[0]) if lines else 0)
@@ -140,3 +140,75 @@ def test_n8_line_names_the_librarys_collective():
   line = json.loads(bench.compact_line(result))
   assert line['config']['collective_backend'] == bench.COLLECTIVE_CABI and line['config']['collective']['bytes'] == 17146728
   assert line['config']['rccl_ranks'] == 8 and line['config']['collective']['us_mean'] == 35.0
+
+
+def _parse(monkeypatch, *argv):
+  import bench
+  monkeypatch.setattr(bench.sys, 'argv', ['bench.py'] + list(argv))
+  return bench.parse()
+
+
+def test_plain_run_is_the_headline_alone(monkeypatch):
+  """Without --full the benchmark times the main line and nothing else: naming a side leg is refused rather than ignored."""
+  args = _parse(monkeypatch, '--gpus', '1', '--steps', '7', '--warmup', '2')
+  assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+  assert _parse(monkeypatch, '--legs', 'main').legs == 'main'
+  assert _parse(monkeypatch, '--full', '--legs', 'spectrum,config5').full
+  for bad in (['--legs', 'spectrum'], ['--legs', 'main,cpu'], ['--steps', '0'], ['--warmup', '-1'],
+              ['--full', '--legs', 'spectrum', '--dump-outputs', 'out']):
+    with pytest.raises(SystemExit):
+      _parse(monkeypatch, *bad)
+
+
+def test_dump_outputs_writes_one_float64_file_per_metric_value(tmp_path):
+  import bench
+  import numpy as np
+
+  class _Values:
+    def __init__(self, a):
+      self.values = a
+  out = {'crps.t': _Values(np.arange(3, dtype=np.float64) / 7), 'mean_rmse.t': _Values(np.ones(3, dtype=np.float32) / 3)}
+  names = bench.dump_outputs(out, str(tmp_path / 'dump'))
+  assert names == ['crps.t', 'mean_rmse.t']
+  for name, v in out.items():
+    got = np.load(tmp_path / 'dump' / f'{name}.npy')
+    assert got.dtype == np.float64 and got.shape == (3,)
+    np.testing.assert_array_equal(got, np.asarray(v.values, dtype=np.float64))
+
+
+def test_cpu_baseline_workers_stay_within_the_usable_cpus(monkeypatch):
+  import bench
+  monkeypatch.setenv('OMP_NUM_THREADS', '3')
+  assert 1 <= bench.usable_cpus() <= 3
+  monkeypatch.delenv('OMP_NUM_THREADS')
+  assert 1 <= bench.usable_cpus() <= (os.cpu_count() or 1)
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_exactly_k_steps_and_dumps_the_last_one(tmp_path):
+  """A plain run: one line with the headline, no side legs, exactly --steps timed launches; --dump-outputs holds the metric
+  values of the last timed step, the same from run to run (seeded inputs, no atomics in the reductions)."""
+  import numpy as np
+  dumps = []
+  for k in (3, 5):
+    d = tmp_path / f'dump{k}'
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--small', '--steps', str(k), '--warmup', '1', '--prewarm-ms',
+                           '0', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-4000:]
+    lines = [l for l in proc.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline'):
+      assert key in line, key
+    assert line['steps'] == k and line['ms_per_step'] > 0 and line['value'] > 0
+    assert 'cpu_baseline' not in line and 'legs' not in line and 'box' not in line
+    full = json.load(open(os.path.join(ROOT, line['full'])))
+    assert full['roofline']['launches_per_step'] == 1 and f'each of the {k} launches' in full['roofline']['kernel_ms_source']
+    names = sorted(f[:-len('.npy')] for f in os.listdir(d))
+    assert names == sorted(full['outputs']['names']) == ['crps.t', 'mean_rmse.t', 'unbiased_mean_rmse.t', 'unbiased_spread_skill.t']
+    got = {n: np.load(d / f'{n}.npy') for n in names}
+    assert all(a.dtype == np.float64 and a.shape == (3,) and np.isfinite(a).all() for a in got.values())
+    np.testing.assert_allclose(got['crps.t'].mean(), full['check']['crps_mean'], rtol=1e-12)
+    dumps.append(got)
+  for n in dumps[0]:
+    np.testing.assert_array_equal(dumps[0][n], dumps[1][n])

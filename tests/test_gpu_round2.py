@@ -337,7 +337,7 @@ def _run_bench(*flags, timeout=600):
 def test_bench_contract_small(ctx):
   """bench.py keeps the driver's contract (one JSON line with value / roofline / config.workload, every leg present) --
   at debugging sizes, so that a broken leg shows up here and not in the round-end run."""
-  out = _run_bench('--small', '--steps', '2', '--warmup', '1', '--cpu-workers', '2')
+  out = _run_bench('--full', '--small', '--steps', '2', '--warmup', '1', '--cpu-workers', '2')
   for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'configs1', 'ensemble',
               'public_chunk', 'spectrum', 'lat_fastest', 'config5'):
@@ -376,10 +376,10 @@ def test_bench_two_ranks_from_a_bare_shell(ctx):
   if torch.cuda.device_count() < 2:
     skipped = _run_bench('--gpus', '2', '--small', '--steps', '2', '--warmup', '1')
     assert skipped.get('skipped') is True and skipped['n_gpus'] == 2 and 'devices' in skipped['reason']
-  out = _run_bench('--gpus', '2', '--backend', 'gloo', '--small', '--steps', '2', '--warmup', '1', '--legs', 'main,config5')
+  out = _run_bench('--gpus', '2', '--backend', 'gloo', '--small', '--steps', '2', '--warmup', '1', '--full', '--legs', 'main,config5')
   assert out['n_gpus'] == 2 and out['config']['collectives_per_step'] == 1.0 and out['config']['backend'] == 'gloo'
   assert abs(out['check']['crps_mean'] - 0.5642) < 0.01
-  one = _run_bench('--small', '--steps', '2', '--warmup', '1', '--legs', 'config5')
+  one = _run_bench('--small', '--steps', '2', '--warmup', '1', '--full', '--legs', 'config5')
   # the sharded, all-reduced result of the streamed suite equals the one-rank result
   assert out['config5']['n_gpus'] == 2 and out['config5']['check']['shape_rmse_z'] == one['config5']['check']['shape_rmse_z']
   np.testing.assert_allclose(out['config5']['check']['rmse_z_mean'], one['config5']['check']['rmse_z_mean'], rtol=1e-12)

@@ -9,7 +9,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ninit = int(sys.argv[1]) if len(sys.argv) > 1 else 120
-sys.argv = ['bench.py', '--legs', 'config5', '--no-cpu', '--config5-inits', str(ninit)]
+sys.argv = ['bench.py', '--full', '--legs', 'config5', '--no-cpu', '--config5-inits', str(ninit)]
 import bench  # noqa: E402
 from weatherbenchx_amd import aggregation, pipeline  # noqa: E402
 

@@ -6,7 +6,7 @@ for round in 1 2; do
   for lib in default "$other"; do
     if [ "$lib" = default ]; then unset WBX_LIBRARY_PATH; else export WBX_LIBRARY_PATH=$PWD/$lib; fi
     python tools/kbench.py ens 2>&1 | grep "block= 64" | grep "sort\|loadonly" | sed "s#^#$lib: #"
-    python bench.py --legs main,ensemble --no-cpu --no-config5 2>/dev/null | python -c "
+    python bench.py --full --legs main,ensemble --no-cpu --no-config5 2>/dev/null | python -c "
 import sys, json
 r = json.loads(sys.stdin.read())
 for k, leg in (("main", r), ("ensemble", r["ensemble"])):

@@ -15,7 +15,7 @@ for rep in 1 2; do
   for lib in libwbx_hip_nodemean.so libwbx_hip.so; do
     export WBX_LIBRARY_PATH=$PWD/weatherbenchx_amd/$lib
     for layout in lon_fastest lat_fastest; do
-      timeout 200 python bench.py --legs spectrum --layout $layout --no-cpu 2>/dev/null | python -c "
+      timeout 200 python bench.py --full --legs spectrum --layout $layout --no-cpu 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())['spectrum']; w=d['with_deterministic_suite']
 print('$lib $layout rep$rep: spectrum kernel_ms', d['roofline']['kernel_ms'], 'frac', d['roofline']['frac'], '| composite ms_per_chunk', round(w['ms_per_chunk'],4), 'kernel_ms', w.get('roofline',{}).get('kernel_ms'), 'sumS', d['check']['sum_k_S_k'])" >> $OUT 2>&1

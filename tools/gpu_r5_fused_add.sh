@@ -9,7 +9,7 @@ OUT=gpurun_out/r5_fused_add.txt
 for rep in 1 2 3; do
 for f in 0 1; do
   for lay in lon_fastest lat_fastest; do
-    WBX_FUSED_ACC_ADD=$f timeout 300 python bench.py --legs public_chunk,public_chunk_ens --no-cpu --no-config5 --steps 5 --warmup 2 --layout $lay > /dev/null 2>>$OUT.err
+    WBX_FUSED_ACC_ADD=$f timeout 300 python bench.py --full --legs public_chunk,public_chunk_ens --no-cpu --no-config5 --steps 5 --warmup 2 --layout $lay > /dev/null 2>>$OUT.err
     python - >> $OUT <<PY
 import json
 d = json.load(open('bench_full.json'))

@@ -12,10 +12,10 @@ for rep in 1 2 3; do
 for tree in ab_r4 .; do
   for lay in lon_fastest lat_fastest; do
     echo "== rep $rep tree $tree $lay" >> $OUT
-    ( cd $R/$tree && rm -f bench_full.json && WBX_CHUNK_REPLAY=0 timeout 300 python bench.py --legs spectrum --no-cpu --no-config5 --steps 10 --warmup 3 --layout $lay > $R/gpurun_out/ab_line.json 2>>$OUT.err
+    ( cd $R/$tree && rm -f bench_full.json && WBX_CHUNK_REPLAY=0 timeout 300 python bench.py --full --legs spectrum --no-cpu --no-config5 --steps 10 --warmup 3 --layout $lay > $OUT.line.json 2>>$OUT.err
       python - >> $OUT <<PY
 import json, os
-d = json.load(open('bench_full.json')) if os.path.exists('bench_full.json') else json.loads(open('$R/gpurun_out/ab_line.json').read().strip().splitlines()[-1])
+d = json.load(open('bench_full.json')) if os.path.exists('bench_full.json') else json.loads(open('$OUT.line.json').read().strip().splitlines()[-1])
 s = d['spectrum']
 w = s.get('with_deterministic_suite', {})
 print('spectrum kernel_ms', s['roofline']['kernel_ms'], 'frac', s['roofline']['frac'], '| composite ms_per_chunk', round(w.get('ms_per_chunk', 0), 4), w.get('roofline', {}).get('kernel_ms'))

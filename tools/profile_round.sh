@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 # 2. kernel traces, one leg per trace; each traced process also prints its own JSON line, so its HIP-event durations and
 # rocprofv3's durations of the SAME launches sit side by side in rNN_events_vs_rocprof.txt
 T="rocprofv3 --kernel-trace --stats"

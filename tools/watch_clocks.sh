@@ -1,7 +1,7 @@
 #!/bin/bash
 # Polls rocm-smi (clocks, power) while a sustained spectrum / main bench loop runs: is the kernel power-throttled?
 LEG=${1:-spectrum}
-timeout 120 python bench.py --legs $LEG --no-cpu --steps 6000 --warmup 3 > gpurun_out/watch_$LEG.json 2>/dev/null &
+timeout 120 python bench.py --full --legs $LEG --no-cpu --steps 6000 --warmup 3 > ${OUT_DIR:-${TMPDIR:-/tmp}}/watch_$LEG.json 2>/dev/null &
 PID=$!
 sleep 14
 for i in 1 2 3 4 5 6; do
@@ -10,4 +10,4 @@ for i in 1 2 3 4 5 6; do
 done
 wait $PID
 python -c "
-import json; d=json.load(open('gpurun_out/watch_$LEG.json')); d=d.get('$LEG', d); print('$LEG', d.get('ms_per_step'))"
+import json; d=json.load(open('${OUT_DIR:-${TMPDIR:-/tmp}}/watch_$LEG.json')); d=d.get('$LEG', d); print('$LEG', d.get('ms_per_step'))"
