@@ -435,13 +435,23 @@ int wbx_ens_map(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype, int M, int64_t
  * sums over rows are fp64).  1440-point rows (0.25 degree grids, both layouts): a row is shifted by an estimate of its mean
  * before the transform and F_0 is restored in fp64, so the error does not scale with the field's mean --
  * |dS_k| <= 2e-6 S_k + 1e-6 sqrt(S'_max S_k), S'_max = max_{k >= 1} S_k, and S_0 to 1e-6, per row against float64 numpy.fft
- * (tests/test_spectra.py::bound_1440); measured on N(0, 1) and N(280, 1) rows: median 1.4e-7, and 1e-7 for every wavenumber
- * after a mean over 200 rows (profiles/r03_spectrum_demean_ab.txt; without the shift the N(280, 1) rows came out at 1e-5
- * in the median and 6e-5 after that mean).  Every other length the generic fused kernel takes (even, 2/3/5-smooth half length,
- * <= 2048 points: the 64- and 240-point grids of the public configs on one-wave teams, 360 / 720 / 1024 points on teams of two
- * or four waves) is shifted the same way and held to the same bound.  The rocFFT route (odd lengths, prime factors > 5)
- * transforms the rows as they are: |dS_k| <= 2e-5 S_k + 4e-7
- * sqrt(S_max S_k) with S_max including the mean. */
+ * (tests/test_spectra.py::bound_1440).  The relative error of S_k depends on how far S_k sits below S'_max, so it is quoted per
+ * kind of row (tests/test_spectra_red.py, profiles/spectrum_accuracy_red_rows.txt; 1440 points, per-row median / area-weighted
+ * mean over 200 rows, wavenumbers 1-9 | 10-99 | 100-299 | 300-599 | 600-720):
+ *   white rows (280 +- 10):      1.1e-7 / <= 1e-7 in every band -- the 1e-7 after a mean over 200 rows holds for white rows only;
+ *   k^-3 rows (temperature-like): 8.5e-8 | 6.3e-7 | 4.3e-6 | 1.5e-5 | 2.8e-5 / 3.4e-8 | 7.1e-7 | 9.0e-6 | 2.0e-5 | 2.2e-5;
+ *   k^-5 rows (geopotential-like, 5.4e4 +- 1e3): 1.5e-7 | 1.8e-5 | 4.6e-4 | 3.8e-3 | 1.1e-2 / up to 1.6e-2 (300-599), 0.18 (600-720).
+ * That is the fp32 floor of any single-precision transform of those rows (tools/spectrum_fp32_floor.py emulates one on the CPU):
+ * per row the one-wave kernels, the generic kernel, the fused det + spectra sweep and the rocFFT route measure 0.5x - 1.6x of
+ * it; after a mean over 200 rows 0.1x - 7.4x (the mean of the floor itself varies several-fold from one set of rows to the
+ * next).  The |dF|^2 term of a coefficient the row has (almost) none of is up to 5e-15 S'_max.  Every other length the
+ * generic fused kernel takes (even, 2/3/5-smooth half length, <= 2048 points: the 64- and 240-point grids of the public
+ * configs on one-wave teams, 360 / 720 / 1024 points on teams of two or four waves) is shifted the same way and held to the
+ * same bound.  The rocFFT route (odd lengths, prime factors > 5, rows that are not 8-byte aligned, WBX_SPECTRUM_PATH=rocfft)
+ * shifts the rows too: a pre-pass (shift_rows_kernel) subtracts each row's mean (fp64 sum, rounded to fp32) into a contiguous
+ * scratch tile, rocFFT transforms that, and power_kernel puts X_0 = X'_0 + n m back in fp64: |dS_k| <= 2e-5 S_k + 4e-7
+ * sqrt(S_max S_k) with S_max including the mean.  F_0 itself: within 5e-16 of the oracle's S_0 on rows near 280 on every
+ * route but the lon-fastest one-wave kernel (8.6e-8, fp32-like, inside its 1e-6; tests/test_spectra_red.py (e)). */
 int wbx_zonal_spectrum(wbx_ctx* ctx, const float* field, int64_t lon_stride, int64_t row_stride, int64_t nrows,
                        int32_t nlon, const int32_t* group, const double* scale, int32_t ngroup,
                        int32_t accumulate, double* power_out);

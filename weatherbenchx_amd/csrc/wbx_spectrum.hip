@@ -54,6 +54,8 @@ struct FftState {
   size_t recs_bytes = 0;  // of recs.data
   std::map<std::tuple<int, int64_t, int64_t, int64_t>, FftPlan> plans;  // (nlon, lon_stride, row_stride, batch)
   void* scratch = nullptr;  // complex tile
+  void* lib_rows = nullptr;  // rocFFT route: the tile's rows shifted by their means (float[tile][nlon]) + the shifts (float[tile])
+  size_t lib_rows_size = 0;
   std::map<int, void*> twiddles;  // nlon -> device float2[n/2] + float2[n/2 + 1] of the fused path
   std::map<std::vector<int64_t>, void*> slab_offsets;  // slab offset lists of latitude-fastest fields, on the device
   std::map<std::pair<const void*, size_t>, int> occupancy;  // (fused kernel, dynamic LDS bytes) -> resident blocks per CU
@@ -73,6 +75,7 @@ void spectrum_release(wbx_ctx* ctx) {
   if (!st) return;
   for (auto& kv : st->plans) destroy_plan(kv.second);
   if (st->scratch) (void)hipFree(st->scratch);
+  if (st->lib_rows) (void)hipFree(st->lib_rows);
   if (st->recs.data) (void)hipFree(st->recs.data);
   if (st->recs.group) (void)hipFree(st->recs.group);
   if (st->recs.key) (void)hipFree(st->recs.key);
@@ -442,10 +445,33 @@ static int spec_close(wbx_ctx* ctx, const SpecRecs& R, int32_t ngroup, int32_t n
 
 // One block = a run of rows x ALL wavenumbers (256 at a time); consecutive rows of the same group are summed in registers and
 // stored as one record per (group change) of the block.  F is [rows][nk] interleaved complex (coalesced along k).
+// rocFFT route, in front of the transform: rows[r][i] = x_r[i] - m_r, shift[r] = m_r = the row's mean (fp64 sum, rounded to fp32;
+// any m is valid, it only has to be close), for rows r = row0 .. row0 + nrows_tile of any stride and alignment -- one block
+// per row.  As in the fused kernels the fp32 transform's error then scales with the row's anomalies instead of its mean, and
+// power_kernel puts X_0 = X'_0 + n m back in fp64 (a shift by a constant changes no other coefficient).
+__global__ void __launch_bounds__(256) shift_rows_kernel(const float* __restrict__ field, int64_t lon_stride, int64_t row_stride,
+                                                         int64_t row0, int nlon, float* __restrict__ rows, float* __restrict__ shift) {
+  __shared__ double part[256];
+  const int64_t r = blockIdx.x;
+  const float* x = field + (row0 + r) * row_stride;
+  double s = 0.0;
+  for (int i = (int)threadIdx.x; i < nlon; i += 256) s += (double)x[(int64_t)i * lon_stride];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float m = (float)(part[0] / (double)nlon);
+  float* y = rows + r * (int64_t)nlon;
+  for (int i = (int)threadIdx.x; i < nlon; i += 256) y[i] = x[(int64_t)i * lon_stride] - m;
+  if (threadIdx.x == 0) shift[r] = m;
+}
+
 __global__ void __launch_bounds__(256) power_kernel(const float2* __restrict__ F, int64_t row0, int64_t nrows_tile,
                                                     int rows_per_block, int nk, int nlon,
                                                     const int32_t* __restrict__ group, const double* __restrict__ scale,
-                                                    SpecRecs recs, int64_t team_base) {
+                                                    SpecRecs recs, int64_t team_base, const float* __restrict__ shift) {
   __shared__ unsigned int rec_slot;
   const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r_end = r_begin + rows_per_block < nrows_tile ? r_begin + rows_per_block : nrows_tile;
@@ -468,7 +494,8 @@ __global__ void __launch_bounds__(256) power_kernel(const float2* __restrict__ F
       double acc = 0.0;
       for (int64_t r = ra; r < rb; ++r) {
         const float2 f = F[r * nk + k];
-        const double re = (double)f.x, im = (double)f.y;
+        // k = 0: X_0 = X'_0 + n m of the row shifted by m (shift_rows_kernel), formed in fp64
+        const double re = (double)f.x + (k == 0 ? (double)nlon * (double)shift[r] : 0.0), im = (double)f.y;
         acc += (re * re + im * im) * norm * scale[row0 + r];
       }
       rec[k] = acc;
@@ -1307,16 +1334,33 @@ static int rocfft_route(wbx_ctx* ctx, FftState* st, const float* field, int64_t 
     WBX_HIP(hipMalloc(&st->scratch, need));
     st->scratch_size = need;
   }
+  // the tile's rows shifted by their means, contiguous (the transform reads them with unit stride), + the shifts
+  const size_t need_rows = (size_t)tile * nlon * sizeof(float) + (size_t)tile * sizeof(float);
+  if (st->lib_rows_size < need_rows) {
+    if (st->lib_rows) {
+      WBX_HIP(hipStreamSynchronize(ctx->stream));
+      WBX_HIP(hipFree(st->lib_rows));
+      st->lib_rows = nullptr;
+      st->lib_rows_size = 0;
+    }
+    WBX_HIP(hipMalloc(&st->lib_rows, need_rows));
+    st->lib_rows_size = need_rows;
+  }
+  float* rows = reinterpret_cast<float*>(st->lib_rows);
+  float* shift = rows + (size_t)tile * nlon;
   for (int64_t r0 = 0; r0 < nrows; r0 += tile) {
     const int64_t n = r0 + tile <= nrows ? tile : nrows - r0;
+    hipLaunchKernelGGL(shift_rows_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, field, lon_stride, row_stride, r0, (int)nlon,
+                       rows, shift);
+    WBX_HIP(hipGetLastError());
     FftPlan* plan = nullptr;
-    if (int rc = get_plan(ctx, st, nlon, lon_stride, row_stride, n, &plan)) return rc;
-    void* in = const_cast<float*>(field + r0 * row_stride);
+    if (int rc = get_plan(ctx, st, nlon, 1, nlon, n, &plan)) return rc;
+    void* in = rows;
     void* out = st->scratch;
     WBX_FFT(rocfft_execute(plan->plan, &in, &out, plan->info));
     const unsigned blocks = (unsigned)((n + rows_per_block - 1) / rows_per_block);
     hipLaunchKernelGGL(power_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const float2*>(st->scratch), r0, n,
-                       rows_per_block, nk, nlon, group, scale, recs, team_base);
+                       rows_per_block, nk, nlon, group, scale, recs, team_base, shift);
     WBX_HIP(hipGetLastError());
     team_base += blocks;
   }
