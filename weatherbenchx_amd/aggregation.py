@@ -492,8 +492,8 @@ class Aggregator:
     return values, counts, out_dims, frame_coords, stat._lane, scale  # pylint: disable=protected-access
 
   def _reduce_categorical(self, stat: 'lazy.LazyCategorical', w_da, bin_dims, use_mask, skipna):
-    """Indicator statistics: every category is a lane of ONE launch (wbx_cat_partial); the categories come back as
-    the statistic's trailing dimension."""
+    """Indicator statistics: every category is a lane of ONE launch (wbx_cat_partial; more thresholds than a launch holds:
+    one launch per block, lazy.FusedGroup._reduce_cat); the categories come back as the statistic's trailing dimension."""
     grp = stat._group  # pylint: disable=protected-access
     cat_dim = stat._cat_dim  # pylint: disable=protected-access
     # every category is a lane of one launch: `values` / `counts` are (category,) + out_dims views of its output

@@ -104,7 +104,6 @@ extern "C" int wbx_ens2_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype
   if (int rc = check_plan(plan)) return rc;
   WBX_REQUIRE(plan->vec == 1 && plan->x_weights == nullptr, "wbx_ens2_partial uses vec = 1 and no folded weights");
   WBX_REQUIRE(M >= 1 && N >= 1, "ensemble sizes must be >= 1 (got %d, %d)", M, N);
-  WBX_REQUIRE(target_member_stride == (int64_t)(int32_t)target_member_stride || target_member_stride >= 0, "bad target member stride");
   if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "WBX_FLAG_MASKED set but mask is NULL");
   const bool empty = plan->nkey * plan->ndepth * plan->nx == 0;
   WBX_REQUIRE(empty || (p != nullptr && t != nullptr), "predictions/targets pointer is NULL");

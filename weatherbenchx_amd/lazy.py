@@ -28,6 +28,18 @@ ENS_LANE = {'CRPSSkill': 0, 'CRPSSpread': 1, 'EnsembleVariance': 2, 'UnbiasedEns
             'EnsembleMeanSquaredError': 4}
 
 
+# Indicator launches keep one column of counters per lane and thread in LDS (csrc/wbx_cat.hip): 64 threads x 8 bytes per
+# exceedance lane (fp64 fractions), x 4 bytes per rank lane (uint32 counts), 64 KB per launch.
+CAT_LDS_BYTES = 64 * 1024
+
+
+def cat_lanes_per_launch(func: int, masked: bool, skipna: bool) -> int:
+  """Value lanes (categories) ONE wbx_cat_partial / wbx_cat_exceed_field launch holds: skipna adds a count lane per value
+  lane, a mask alone one shared count lane.  Exceedance: 128 / 127 / 64 thresholds; rank histogram: 256 / 255 / 128 ranks."""
+  lanes = CAT_LDS_BYTES // (64 * (4 if func == _hip.CAT_RANK else 8))
+  return lanes // 2 if skipna else (lanes - 1 if masked else lanes)
+
+
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
 
 
@@ -204,10 +216,52 @@ class FusedGroup:
       return engine.reduce_statistics('ens2', inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce),
                                       w_da, bin_dims, mask=mask, skipna=skipna, ens=self.ens)
     if self.kind == 'cat':
-      return engine.reduce_statistics('cat', inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce),
-                                      w_da, bin_dims, mask=mask, skipna=skipna, cat=self.cat)
+      return self._reduce_cat(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
     return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
                                bin_dims, func=func, mask=mask, skipna=skipna, clim=self.clim, ens=ens)
+
+  def _reduce_cat(self, inputs, reduce_dims, w_da, bin_dims, mask, skipna):
+    """Indicator statistics: one launch where the categories fit its LDS columns (cat_lanes_per_launch), else -- thresholds
+    are independent of one another -- one launch per block of categories that fits, the results joined along the category
+    axis.  The ranks of a histogram are not independent (a point adds to ONE of its M + 1 bins, whichever): no split."""
+    cat = self.cat
+    ncat, func = int(cat['ncat']), int(cat['func'])
+    block = cat_lanes_per_launch(func, mask is not None, skipna)
+    if ncat > block and func == _hip.CAT_RANK:
+      how = 'with skipna' if skipna else ('under a mask' if mask is not None else 'without mask and skipna')
+      raise ValueError(f'RankHistogram: {ncat - 1} members need {ncat} rank lanes, but one launch holds {block} {how} '
+                       f'(at most {block - 1} members); the ranks of a histogram cannot be split over launches')
+    if ncat <= block:
+      return engine.reduce_statistics('cat', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                      skipna=skipna, cat=cat)
+    values, counts, out_dims = [], [], None
+    with engine.synchronous_results():  # the blocks are joined on the host right away
+      for sub in self._cat_blocks(block):
+        v, c, out_dims = engine.reduce_statistics('cat', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                                  skipna=skipna, cat=sub)
+        values.append(np.array(v, dtype=np.float64))  # (own memory: the next launch reuses the result buffers)
+        counts.append(np.array(c, dtype=np.float64))
+    return np.concatenate(values, axis=0), np.concatenate(counts, axis=0), out_dims
+
+  def _cat_blocks(self, block: int):
+    """self.cat cut into runs of at most `block` categories (kept: a block's threshold table / field is uploaded once)."""
+    memo = self.__dict__.setdefault('_cat_block_memo', {})
+    if block not in memo:
+      cat, subs = self.cat, []
+      for k0 in range(0, int(cat['ncat']), block):
+        k1 = min(k0 + block, int(cat['ncat']))
+        sub = dict(cat, ncat=k1 - k0)
+        if cat.get('thr_field') is not None:
+          field, cdim = cat['thr_field'], cat['cat_dim']
+          ax = field.dims.index(cdim)
+          vals = np.ascontiguousarray(np.take(np.asarray(field.values, np.float64), np.arange(k0, k1), axis=ax))
+          sub['thr_field'] = xr.DataArray(vals, dims=field.dims, coords={d: field.coords[d].values for d in field.dims
+                                                                         if d != cdim and d in field.coords})
+        else:
+          sub['thresholds'] = np.ascontiguousarray(cat['thresholds'][k0:k1])
+        subs.append(sub)
+      memo[block] = subs
+    return memo[block]
 
   def materialise(self, lane: int, ens_params=None) -> np.ndarray:
     if self.kind == 'ens2':  # stage 1 with every dim kept IS the per-point statistic
@@ -464,8 +518,9 @@ def ens_statistic(stat_name: str, p, t, ensemble_dim: str, *, use_sort=False, fa
 
 class LazyCategorical(xr.LazyPickleMixin, xr.DataArray):
   """An indicator statistic (ErrorExceedance, EnsembleErrorExceedance, RankHistogram): the frame of (p, t) plus ONE new
-  trailing dimension of categories.  The Aggregator reduces all categories in one launch (wbx_cat_partial); reading
-  `.data` evaluates the same kernel without reducing anything.
+  trailing dimension of categories.  The Aggregator reduces all categories in one launch (wbx_cat_partial) -- or, past what a
+  launch's LDS columns hold, in one launch per block of thresholds (FusedGroup._reduce_cat); reading `.data` evaluates the
+  same kernel without reducing anything.
 
   `split` = (dims, shape, coords): the kernel's category axis stands for these trailing dims -- none (a threshold field that
   adds no dimension: one category, squeezed out) or several (a field that adds two or more: stacked for the kernel)."""
