@@ -80,16 +80,15 @@ timeout 600 $B --steps 20 --warmup 5 --layout lat_fastest --no-cpu > $O/bench_n1
 for d in $O/trace_*; do cp $d/r1_kernel_stats.csv $O/$(basename $d)_kernel_stats.csv 2>/dev/null; done
 # 4. same-box A/B and ceilings: the ensemble kernel variants, the fused spectra + deterministic kernel, the read stream
 ( cd $R && python tools/kbench.py ens ) > $O/kbench_ens.txt 2>&1
-( cd $R && for layout in lon_fastest lat_fastest; do for v in default $( [ -f $R/weatherbenchx_amd/libwbx_hip_stats64.so ] && echo stats64 ); do if [ $v = default ]; then unset WBX_LIBRARY_PATH; else export WBX_LIBRARY_PATH=$R/weatherbenchx_amd/libwbx_hip_$v.so; fi; for pipe in 1 0; do echo "== $layout library $v WBX_ENS_PIPE=$pipe"; WBX_ENS_PIPE=$pipe python bench.py --legs main --no-cpu --no-config5 --steps 20 --warmup 5 --layout $layout 2>/dev/null | python -c "import sys, json; r = json.loads(sys.stdin.read()); print('ms_per_step', round(r['ms_per_step'], 4), 'kernel', r['roofline']['kernel'].split(' (')[0], 'kernel_ms', r['roofline']['kernel_ms'], r['roofline']['kernel_ms_min_max'], 'frac', r['roofline']['frac'])"; done; done; done; unset WBX_LIBRARY_PATH ) > $O/ens_pipe_ab.txt 2>&1
-# (kernels these five exercise did not change since r03: WBX_ROUND_FULL=1 re-measures them, make ab-zdlds first)
+( cd $R && for layout in lon_fastest lat_fastest; do for pipe in 1 0; do echo "== $layout library default WBX_ENS_PIPE=$pipe"; WBX_ENS_PIPE=$pipe python bench.py --legs main --no-cpu --no-config5 --steps 20 --warmup 5 --layout $layout 2>/dev/null | python -c "import sys, json; r = json.loads(sys.stdin.read()); print('ms_per_step', round(r['ms_per_step'], 4), 'kernel', r['roofline']['kernel'].split(' (')[0], 'kernel_ms', r['roofline']['kernel_ms'], r['roofline']['kernel_ms_min_max'], 'frac', r['roofline']['frac'])"; done; done ) > $O/ens_pipe_ab.txt 2>&1
+# (kernels these five exercise did not change since r03: WBX_ROUND_FULL=1 re-measures them)
 if [ "${WBX_ROUND_FULL:-0}" = 1 ]; then
 ( cd $R/tools/ubench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 flat_fetch.hip -o /tmp/flat_fetch 2>/dev/null && cd /tmp && for shift in 0 16; do /tmp/flat_fetch $shift; timeout 120 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_REQ_sum --kernel-trace -d $O/ff$shift -o r -- /tmp/flat_fetch $shift > /dev/null 2>&1; python -c "
 import sqlite3
 for k, c, n, v in sqlite3.connect('$O/ff$shift/r_results.db').execute(\"select substr(kernel_name, 1, 44), counter_name, count(*), avg(value) from counters_collection where kernel_name like '%_kernel<%' group by 1, 2\"): print('   shift $shift', k, c, n, '%.0f' % v)"; done; rm -rf $O/ff0 $O/ff16 ) > $O/flat_fetch.txt 2>&1
 ( cd $R/tools/ubench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 column_walk.hip -o /tmp/column_walk 2>/dev/null && /tmp/column_walk ) > $O/column_walk.txt 2>&1
 ( cd $R && bash tools/gpu_r3_ragged_walk.sh ) > $O/ragged_walk.txt 2>&1
-( cd $R && bash tools/gpu_r3_ragged_wpb.sh ) > $O/ragged_wpb.txt 2>&1
-( cd $R && python tools/kbench_det_spectrum.py; echo "== climatology row through the LDS (make ab-zdlds)"; WBX_LIBRARY_PATH=$R/weatherbenchx_amd/libwbx_hip_zdlds.so python tools/kbench_det_spectrum.py ) > $O/kbench_det_spectrum.txt 2>&1
+( cd $R && python tools/kbench_det_spectrum.py ) > $O/kbench_det_spectrum.txt 2>&1
 fi
 ( cd $R/tools/ubench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 read_stream.hip -o read_stream 2>/dev/null; timeout 120 ./read_stream ) > $O/read_stream.json 2>&1
 ( cd $R && bash tools/pmc_ens.sh ) > $O/pmc_ens.txt 2>&1

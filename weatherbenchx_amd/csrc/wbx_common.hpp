@@ -25,7 +25,6 @@ struct wbx_ctx {
   void* atoms_clean = nullptr;  // std::set<const void*>*: prepared atom tables (wbx_binned_atoms) without an overflowing patch
   void* patch_counters = nullptr;  // wbx_ens_binned: arrival counters of its in-kernel sums over patches (uint32, kept zero)
   size_t patch_counters_size = 0;
-  uint32_t ens_queue_parity = 0;   // which of the two ticket sets at the head of patch_counters the next persistent launch uses
   hipEvent_t* marks = nullptr;  // wbx_mark: timing events, created on demand and recycled by wbx_marks_reset
   int marks_used = 0, marks_made = 0, marks_cap = 0;
 };
@@ -47,11 +46,7 @@ inline int fail(int code, const char* fmt, ...) {
 // L2 / Infinity Cache.  Measured on the configs[1] kernel: 6.12 -> 6.45 TB/s (76.5 % -> 80.6 % of the HBM peak).
 template <typename T>
 __device__ __forceinline__ T ld_stream(const T* p) {
-#ifdef WBX_LD_STREAM_PLAIN  // A/B build (make ab-plainld): the same loads without the hint
-  return *p;
-#else
   return __builtin_nontemporal_load(p);
-#endif
 }
 
 // A wave-uniform pointer the compiler also KNOWS to be uniform (SGPR pair): row offsets come out of tables through vector

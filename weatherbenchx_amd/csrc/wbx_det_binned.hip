@@ -31,10 +31,7 @@ namespace wbx {
 // waves per block = adjacent x tiles walked side by side (see patch_decode).  Measured on the public-benchmark chunk:
 // 4 waves per block 0.86 / 0.90 ms (latitude- / longitude-fastest) against 0.80 / 0.77 ms for lone waves -- the wider
 // block spreads an XCD's L2 over 4x the weight / membership rows and buys nothing at the DRAM, so 1 it is.
-#ifndef WBX_BINNED_WPB
-#define WBX_BINNED_WPB 1
-#endif
-constexpr int BINNED_WPB = WBX_BINNED_WPB;
+constexpr int BINNED_WPB = 1;
 
 
 // MM: 0 none, 1 mask only (one shared count lane), 2 skipna (count lane per value lane), 3 skipna + mask.
@@ -248,38 +245,22 @@ __global__ void __launch_bounds__(64 * BINNED_WPB) det_binned_kernel(S1Args a, B
 // themselves): the mask byte and the atom-id byte of a point are ONE byte, 255 = masked out (aid_merge_kernel, a 1 MB
 // pre-pass per launch).  The kernel is bound by the texture addresser -- a wave64 load costs it 16 cycles whatever its width,
 // and a row was five of them (p, t, c, mask, atom id): four now.
-template <typename T, int FUNC, int MM, int PD, int WM, bool NT, bool MERGED = false>
-#ifndef WBX_ATOMS_WAVES
-#define WBX_ATOMS_WAVES 4  // waves per SIMD the register budget is cut for (111 VGPRs as it falls)
-#endif
+constexpr int ATOMS_WAVES = 4;  // waves per SIMD the register budget is cut for (111 VGPRs as it falls)
 // On such rows (!NT) a block is FOUR waves on adjacent x tiles of one row range, meeting at a barrier every 64 rows: the line
 // two tiles share is asked for by both within a few rows and from one CU.  Same-box A/B on the latitude-fastest public chunk,
-// 1 / 2 / 3 / 4 / 6 / 12 waves per block (`make ab-wpb1 ...`, tools/gpu_r3_ragged_wpb.sh): 0.449 / 0.427 (one box: 0.434 /)
+// 1 / 2 / 3 / 4 / 6 / 12 waves per block (profiles/r03_ragged_wpb.txt): 0.449 / 0.427 (one box: 0.434 /)
 // 0.427 / 0.440 / 0.428 / 0.493 / 0.465 ms -- 4 is 4-5 % faster than 1 on both boxes, 4 without the barrier 3.7 %; 6 and 12
 // leave wave slots of the CU empty (16 per CU at 111 VGPRs).
-#ifndef WBX_ATOMS_RAGGED_WPB
-#define WBX_ATOMS_RAGGED_WPB 4
-#endif
-#ifndef WBX_ATOMS_PD
-#define WBX_ATOMS_PD 4  // rows of p, t, c in flight per wave
-#endif
-#ifndef WBX_ATOMS_WAVES_COUNTS
-#define WBX_ATOMS_WAVES_COUNTS 3  // waves per SIMD of the flavours with one count lane per statistic (MM >= 2: Aggregator(skipna=True)): twice the
-                                  // accumulators; at four waves (128 VGPRs) they spilled 152-184 B per lane
-#endif
-#ifndef WBX_ATOMS_KNOCK
-#define WBX_ATOMS_KNOCK 0  // 1: timing diagnostic, see `accumulate`
-#endif
-#ifndef WBX_ATOMS_VPTR
-#define WBX_ATOMS_VPTR 1   // 0: row offsets stepped in scalar registers (rounds 3-5; A/B: make ab-novptr)
-#endif
-#ifndef WBX_ATOMS_SKIP
-#define WBX_ATOMS_SKIP 1   // 0: both entries' FMAs issued every row under EXEC masks (A/B: make ab-atoms6)
-#endif
-__global__ void __launch_bounds__(64 * (NT ? 1 : WBX_ATOMS_RAGGED_WPB))
-__attribute__((amdgpu_waves_per_eu(MM >= 2 ? WBX_ATOMS_WAVES_COUNTS : WBX_ATOMS_WAVES, MM >= 2 ? WBX_ATOMS_WAVES_COUNTS : WBX_ATOMS_WAVES)))
+constexpr int ATOMS_RAGGED_WPB = 4;
+constexpr int ATOMS_PD = 4;  // rows of p, t, c in flight per wave
+// waves per SIMD of the flavours with one count lane per statistic (MM >= 2: Aggregator(skipna=True)): twice the accumulators; at
+// four waves (128 VGPRs) they spilled 152-184 B per lane
+constexpr int ATOMS_WAVES_COUNTS = 3;
+template <typename T, int FUNC, int MM, int PD, int WM, bool NT, bool MERGED = false>
+__global__ void __launch_bounds__(64 * (NT ? 1 : ATOMS_RAGGED_WPB))
+__attribute__((amdgpu_waves_per_eu(MM >= 2 ? ATOMS_WAVES_COUNTS : ATOMS_WAVES, MM >= 2 ? ATOMS_WAVES_COUNTS : ATOMS_WAVES)))
 det_atoms_kernel(S1Args a, BinnedArgs g) {
-  constexpr int W = NT ? 1 : WBX_ATOMS_RAGGED_WPB;
+  constexpr int W = NT ? 1 : ATOMS_RAGGED_WPB;
   constexpr int NIN = FUNC == WBX_DET6 ? 3 : (FUNC == WBX_DET3 ? 2 : 1);
   constexpr int NL = FUNC == WBX_DET6 ? 6 : (FUNC == WBX_DET3 ? 3 : 1);
   constexpr int NC = MM == 1 ? 1 : (MM >= 2 ? NL : 0);
@@ -332,13 +313,7 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
   // Flush BOTH entries of EVERY lane into the LDS table and empty the caches: lanes are grouped by atom id, one DPP wave
   // sum per (group, statistic).  Evicting lane by lane was measured 1.3x slower overall: after a region edge every lane
   // drops its stale entries at a different row (when it next crosses a coast), and each of those rows paid a flush.
-  auto flush_all = [&](bool at_end = true) {
-#ifdef WBX_DIAG_NOFLUSH  // timing diagnostic (wrong sums): what do the flushes in the middle of a sweep cost?
-    if (!at_end) {
-      c0 = c1 = NONE;
-      return;
-    }
-#endif
+  auto flush_all = [&]() {
 #pragma unroll 1
     for (int e = 0; e < 2; ++e) {  // (not unrolled: this code is inlined at every row position of the sweeps)
       const int id = e ? c1 : c0;
@@ -371,18 +346,13 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
   auto accumulate = [&](T tp, T tt, T tc, uint8_t tv, double w, int id) {
     const unsigned long long m_ok = live_mask & (MERGED ? __builtin_amdgcn_ballot_w64(id != NONE) : __builtin_amdgcn_ballot_w64(tv != 0));
     unsigned long long n0 = __builtin_amdgcn_ballot_w64(id != c0), n1 = __builtin_amdgcn_ballot_w64(id != c1);
-#if WBX_ATOMS_KNOCK >= 1  // timing diagnostic (wrong sums): every point goes to entry 0 as atom 0, no hit / miss bookkeeping
-    c0 = 0;
-    n0 = 0ull;
-    n1 = ~0ull;
-#endif
     const bool ok = __builtin_amdgcn_inverse_ballot_w64(m_ok);
-    if (WBX_ATOMS_KNOCK == 0 && (m_ok & n0 & n1)) {  // wave-uniform: a lane meets an atom it is not accumulating
+    if (m_ok & n0 & n1) {  // wave-uniform: a lane meets an atom it is not accumulating
       const bool miss = __builtin_amdgcn_inverse_ballot_w64(m_ok & n0 & n1);
       // a lane with both entries taken meets a third atom (a region edge: the same row for most lanes): start over
       bool place = miss;
       if (__builtin_amdgcn_ballot_w64(miss && c0 != NONE && c1 != NONE)) {
-        flush_all(false);
+        flush_all();
         place = ok;  // every entry is empty now: the lanes that had a hit re-enter their atom too
       }
       if (place && c0 == NONE) c0 = id;
@@ -390,77 +360,57 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
       n0 = __builtin_amdgcn_ballot_w64(id != c0);
       n1 = __builtin_amdgcn_ballot_w64(id != c1);
     }
-#if WBX_ATOMS_SKIP
     // (r6) the entries' masks carry `ok` themselves and the values are formed on every lane (clamped loads: any lane holds a real
     // element): one exec save / restore and one branch per row less than `if (ok) { ... }` around it all
     const bool hit0 = __builtin_amdgcn_inverse_ballot_w64(m_ok & ~n0), hit1 = __builtin_amdgcn_inverse_ballot_w64(m_ok & ~n1);
-    {
-#else
-    const bool hit0 = __builtin_amdgcn_inverse_ballot_w64(~n0), hit1 = __builtin_amdgcn_inverse_ballot_w64(~n1);
-    if (ok) {
-#endif
-      const double p = (double)tp, t = (double)tt, c = (double)tc;
-      double val[NA];
-      if constexpr (FUNC == WBX_PASS1) {
-        val[0] = p;
-      } else {
-        const double e = p - t;
-        val[0] = e;
-        val[1] = fabs(e);
-        val[2] = e * e;
-        if constexpr (FUNC == WBX_DET6) {
-          const double pa = p - c, ta = t - c;
-          val[3] = pa * pa;
-          val[4] = ta * ta;
-          val[5] = pa * ta;
-        }
+    const double p = (double)tp, t = (double)tt, c = (double)tc;
+    double val[NA];
+    if constexpr (FUNC == WBX_PASS1) {
+      val[0] = p;
+    } else {
+      const double e = p - t;
+      val[0] = e;
+      val[1] = fabs(e);
+      val[2] = e * e;
+      if constexpr (FUNC == WBX_DET6) {
+        const double pa = p - c, ta = t - c;
+        val[3] = pa * pa;
+        val[4] = ta * ta;
+        val[5] = pa * ta;
       }
-      if constexpr (MM == 1) val[NL] = 1.0;
-      if constexpr (MM >= 2) {
+    }
+    if constexpr (MM == 1) val[NL] = 1.0;
+    if constexpr (MM >= 2) {
 #pragma unroll
-        for (int l = 0; l < NL; ++l) {
-          const bool fin = !(val[l] != val[l]);
-          val[NL + l] = fin ? 1.0 : 0.0;
-          val[l] = fin ? val[l] : 0.0;
-        }
+      for (int l = 0; l < NL; ++l) {
+        const bool fin = !(val[l] != val[l]);
+        val[NL + l] = fin ? 1.0 : 0.0;
+        val[l] = fin ? val[l] : 0.0;
       }
-      // each entry's FMAs run under its own lane mask (EXEC = the lanes whose point belongs to that entry) with the weight
-      // as it is -- a scalar register for row weights: no `hit ? w : 0` selects (four v_cndmask + two v_mov per row), and a
-      // row in which no lane uses an entry skips that entry's FMAs
-#if WBX_ATOMS_SKIP
-      // (r6) ... and the skip is real: the compiler predicates so short a block with EXEC and drops the `s_cbranch_execz` around
-      // it (SIInsertSkips keeps a branch only over 12+ instructions, or over something with side effects), so the six fp64 FMAs
-      // of an entry no lane is in were ISSUED row after row -- in the interior of a region every lane sits in one entry.  The
-      // empty asm statement is that side effect: six fp64 instructions less per row whenever an entry is idle.
-      if (hit0) {
-        asm volatile("");
+    }
+    // each entry's FMAs run under its own lane mask (EXEC = the lanes whose point belongs to that entry) with the weight
+    // as it is -- a scalar register for row weights: no `hit ? w : 0` selects (four v_cndmask + two v_mov per row), and a
+    // row in which no lane uses an entry skips that entry's FMAs
+    // (r6) ... and the skip is real: the compiler predicates so short a block with EXEC and drops the `s_cbranch_execz` around
+    // it (SIInsertSkips keeps a branch only over 12+ instructions, or over something with side effects), so the six fp64 FMAs
+    // of an entry no lane is in were ISSUED row after row -- in the interior of a region every lane sits in one entry.  The
+    // empty asm statement is that side effect: six fp64 instructions less per row whenever an entry is idle.
+    if (hit0) {
+      asm volatile("");
 #pragma unroll
-        for (int l = 0; l < NA; ++l) acc0[l] = fma(val[l], w, acc0[l]);
-      }
-      if (hit1) {
-        asm volatile("");
+      for (int l = 0; l < NA; ++l) acc0[l] = fma(val[l], w, acc0[l]);
+    }
+    if (hit1) {
+      asm volatile("");
 #pragma unroll
-        for (int l = 0; l < NA; ++l) acc1[l] = fma(val[l], w, acc1[l]);
-      }
-#else
-      if (hit0) {
-#pragma unroll
-        for (int l = 0; l < NA; ++l) acc0[l] = fma(val[l], w, acc0[l]);
-      }
-      if (hit1) {
-#pragma unroll
-        for (int l = 0; l < NA; ++l) acc1[l] = fma(val[l], w, acc1[l]);
-      }
-#endif
+      for (int l = 0; l < NA; ++l) acc1[l] = fma(val[l], w, acc1[l]);
     }
   };
 
   for (int64_t rb = rbeg; rb < rend; rb += 64) {
     // W > 1: the waves of a block walk ADJACENT x tiles of the same rows and meet here every 64 rows, so a boundary line two
     // tiles share is asked for by both within a few rows of each other (waves that have left the kernel do not count)
-#ifndef WBX_ATOMS_RAGGED_NOBARRIER  // (A/B: side by side on one CU, free-running)
     if constexpr (W > 1) __builtin_amdgcn_s_barrier();
-#endif
     // lane j resolves row rb + j through the plan's tables (key / depth offsets, the climatology gather)
     const int64_t rmine = rb + lane < rend ? rb + lane : rend - 1;
     // (a 64-bit divide is a ~250-instruction sequence, paid per 64 rows: the row count fits 31 bits on every real chunk)
@@ -513,7 +463,6 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
       // EVEN: the row offsets of the NEXT fetch, stepped by scalar additions.  Fetches ask for rows 0, 1, 2, ... in order and
       // stay on the last row once they reach it, so `base + j * step` (a 64-bit scalar multiplication per input and row:
       // 24 of the 41 scalar instructions a row cost in round 2; public chunk 0.443 -> 0.415 ms) is never needed.
-#if WBX_ATOMS_VPTR
       // (r6) EVEN: the address of the NEXT fetch as a per-lane 64-bit pointer per operand, advanced by ONE vector add (the step sits
       // in a scalar pair).  Round 3 kept the row offsets as scalars -- two scalar adds per operand and row -- and the compiler
       // formed every load's address with a 64-bit vector add on top of that anyway (`v_lshl_add_u64 v, s[row], 2, v[lane base]`):
@@ -565,40 +514,6 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
           if constexpr (WM == 2) S.w[u] = __longlong_as_double(readlane64(__double_as_longlong(wrow_w), j));
         }
       };
-#else
-      int64_t cur[WBX_MAX_INPUTS + 1];
-#pragma unroll
-      for (int i = 0; i <= WBX_MAX_INPUTS; ++i) cur[i] = EVEN ? readlane64(i == WBX_MAX_INPUTS ? wrow_v : ro[i], 0) : 0;
-      auto row_of = [&](int i, int j) -> int64_t {
-        if constexpr (EVEN) return cur[i];
-        return readlane64(i == WBX_MAX_INPUTS ? wrow_v : ro[i], j);
-      };
-      auto fetched = [&](int j, auto inside_tag) {  // row j has just been asked for
-        if constexpr (EVEN) {
-          const bool more = decltype(inside_tag)::value || j < last;  // inside: row j + 1 exists, no test
-#pragma unroll
-          for (int i = 0; i <= WBX_MAX_INPUTS; ++i) cur[i] += more ? step[i] : 0;
-        }
-      };
-      auto operand = [&](int i, int j) -> T {
-        const T* q = (reinterpret_cast<const T*>(a.in[i]) + row_of(i, j)) + xo[i];
-        if constexpr (NT) return ld_stream(q);
-        return *q;
-      };
-      auto fetch = [&](Slots& S, int j, int u, auto inside_tag) {
-        S.p[u] = operand(0, j);
-        if constexpr (NIN > 1) S.t[u] = operand(1, j);
-        if constexpr (NIN > 2) S.c[u] = operand(2, j);
-        S.v[u] = 1;
-        if constexpr (has_mask && !MERGED) S.v[u] = (reinterpret_cast<const uint8_t*>(a.in[3]) + row_of(3, j))[xo[3]];
-        const int64_t wi = row_of(WBX_MAX_INPUTS, j);
-        S.id[u] = ((MERGED ? g.aidm : g.aid) + wi)[xw];
-        if constexpr (WM == 0) S.w[u] = (g.wt + wi)[xw];
-        if constexpr (WM == 1) S.w[u] = w_lane;
-        if constexpr (WM == 2) S.w[u] = __longlong_as_double(readlane64(__double_as_longlong(wrow_w), j));
-        fetched(j, inside_tag);
-      };
-#endif
       // every load is unconditional (clamped row indices), see det_binned_kernel
       Slots A;
 #pragma unroll
@@ -687,7 +602,7 @@ static int launch_binned_k(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, con
     return rc;
   const int64_t grid = patch_grid<BINNED_WPB>(g);
   if (atoms) {
-    constexpr int RW = WBX_ATOMS_RAGGED_WPB;
+    constexpr int RW = ATOMS_RAGGED_WPB;
     const int64_t agrid1 = patch_grid<1>(g), agridw = patch_grid<RW>(g);
     static const int order_env = atoms_setting("WBX_PATCH_ORDER", -1);
     static const int nt_env = atoms_setting("WBX_ATOMS_NT", -1);
@@ -722,7 +637,7 @@ static int launch_binned_k(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, con
     } while (0)
     // (4 rows in flight per wave; 2 / 4 / 8 were measured 0.61 / 0.59 / 0.63 ms and the variants dropped: they doubled the
     // 144 instantiations of this kernel and the build time of this file)
-    if (wmode == 1) WBX_ATOMS_LAUNCH(WBX_ATOMS_PD, 1); else if (wmode == 2) WBX_ATOMS_LAUNCH(WBX_ATOMS_PD, 2); else WBX_ATOMS_LAUNCH(WBX_ATOMS_PD, 0);
+    if (wmode == 1) WBX_ATOMS_LAUNCH(ATOMS_PD, 1); else if (wmode == 2) WBX_ATOMS_LAUNCH(ATOMS_PD, 2); else WBX_ATOMS_LAUNCH(ATOMS_PD, 0);
 #undef WBX_ATOMS_LAUNCH_NT
 #undef WBX_ATOMS_LAUNCH
 #undef g

@@ -51,12 +51,7 @@ constexpr int ENS_ATOMS_NOUT = 6;  // written per (cell, bin): the five ensemble
 constexpr int ENS_ATOMS_NOUT2 = 12;  // ... and, in twin mode, the same six again over ALL points (mask ignored)
 constexpr int ENS_ATOMS_ROWS2 = 2 * ATOM_MAX;  // table rows per patch: an atom and its twin (the masked-out points of the atom)
 
-#ifndef WBX_EA_KNOCK
-#define WBX_EA_KNOCK 0  // diagnostic builds only (make ab-eak1 / ab-eak2)
-#endif
-#ifndef WBX_ENS_ATOMS_ROWS
-#define WBX_ENS_ATOMS_ROWS 16  // rows (= 64-point tiles) per patch; WBX_ENS_ATOMS_ROWS in the environment overrides
-#endif
+constexpr int64_t ENS_ATOMS_ROWS = 16;  // rows (= 64-point tiles) per patch; WBX_ENS_ATOMS_ROWS in the environment overrides
 
 // (global_ptr / const_ptr and the stand-in tables wbx_zero_i64 / wbx_one_f64: wbx_common.hpp)
 
@@ -107,9 +102,9 @@ struct EnsAtomsArgs {
   double* part1;       // [cell][ng1][NOUT][64]
   double* part2;       // [cell][ng2][NP]
   uint32_t* counters;  // [cell][ng1] | [cell][ng2] | [cell], zero before the first launch and after every launch
-  uint32_t* queue;     // persistent launches: [64] patch tickets, one queue per (XCD, eighth of its patches); zero at launch
-  int32_t queue_static;  // A/B (WBX_ENS_ATOMS_STATIC=1): no tickets, a fixed share of the patches per wave
-  uint32_t* queue_next;  // the next launch's [64]: zeroed by this one (nobody else touches it meanwhile: stream order)
+  uint32_t* unused0;   // unused0 .. unused3: read by nobody, always zero.  They keep the kernel-argument layout the kernel was tuned
+  int32_t unused1;     // with: without them the compiler lays ens_atoms_kernel's scalar loads and SGPR spills out differently all
+  uint32_t* unused2;   // through the sweep (other instruction counts in all 42 instantiations, 105 -> 106 SGPRs in <51, NT, MODE 1>)
   double* out;         // [cell][NOUT][nbin]
   int32_t ng1, ng2;
   int32_t masked;      // 0: no mask; 1: the atom ids are g.aidm, 255 = masked out; 2 (twin): g.aidm, id | 0x80 = masked out -- such
@@ -123,31 +118,14 @@ struct EnsAtomsArgs {
   int64_t id_cell_rows;  // 0: the id bytes are [bk][br][nj] (bins / a mask on the W dims); R = nBr * D: one id byte per point,
                          // [cell][r][nj] (a mask with strides along A / the depth dims)
   int64_t br_per_split;  // g.rows_per_split / D
-  unsigned long long* prof;  // diagnostic builds (WBX_EA_PROF): eight time stamps per patch, else NULL
+  unsigned long long* unused3;
 };
 
-#ifndef WBX_ENS_ATOMS_ROW_BARRIER
-#define WBX_ENS_ATOMS_ROW_BARRIER 4  // rows between two block barriers of the ragged-row flavour (power of two; 0 = none: make
-                                     // ab-eabar0).  (r6) 4: the four waves of a block -- adjacent x tiles of the same rows -- ask for
-                                     // the 128-byte lines two tiles share within the few microseconds a streamed line survives in the
-                                     // XCD's L2: FETCH_SIZE x 2 = 1.076 x the algorithmic bytes instead of 1.141 x (NaN mask 1.10
-                                     // instead of 1.17) at the same time per chunk (profiles/r06_ens_atoms_rowbarrier.txt)
-#endif
-#ifndef WBX_EA_PERSIST
-#define WBX_EA_PERSIST 0  // make ab-eapersist: persistent waves on one-wave blocks (see ens_atoms_kernel<.., PERSIST>); measured
-#endif                    // SLOWER than one block per patch (profiles/r05_ens_atoms_persistent_ab.txt) and not in the shipped library
-#ifndef WBX_EA_PERSIST_RELOAD
-#define WBX_EA_PERSIST_RELOAD 1  // make ab-eanoreload: the persistent kernel keeps its arguments in registers across patches
-#endif
-#ifndef WBX_EA_PROF
-#define WBX_EA_PROF 0  // make ab-eaprof: phase stamps of every wave, dumped to $WBX_EA_PROF_DUMP after each launch
-#endif
-#if WBX_EA_PROF
-#define WBX_EA_STAMP(slot) \
-  do { if (lane == 0) e.prof[(cell * npatch + patch) * 16 + (slot)] = wall_clock64(); } while (0)
-#else
-#define WBX_EA_STAMP(slot) do {} while (0)
-#endif
+// Rows between two block barriers of the ragged-row flavour (power of two).  The four waves of a block -- adjacent x tiles of the
+// same rows -- ask for the 128-byte lines two tiles share within the few microseconds a streamed line survives in the XCD's L2:
+// FETCH_SIZE x 2 = 1.076 x the algorithmic bytes instead of 1.141 x without a barrier (NaN mask 1.10 instead of 1.17) at the same
+// time per chunk (profiles/r06_ens_atoms_rowbarrier.txt)
+constexpr int ENS_ATOMS_ROW_BARRIER = 4;
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"  // m0 is written by the LDS-DMA statements and listed as clobbered
@@ -156,50 +134,19 @@ struct EnsAtomsArgs {
 // of each other and the second request finds them in the CU's L1 / the XCD's L2 (alone, the neighbouring tile is another wave
 // somewhere on the XCD, up to a patch length away in time, and the line has left the L2 by then: FETCH_SIZE 1.28 x the
 // algorithmic bytes on the latitude-fastest public chunk).  Used with !NT (rows that are not whole lines), like det_atoms_kernel.
-#ifndef WBX_ENS_ATOMS_RAGGED_WPB
-#define WBX_ENS_ATOMS_RAGGED_WPB 4
-#endif
+constexpr int ENS_ATOMS_RAGGED_WPB = 4;
 // MODE 0: the id bytes are [bk][br][x] (bins, or bins + a mask on the W dims) -- the round-4 kernel, nothing added to its loop;
 //      1: one id byte per point of the chunk (a mask with strides along A / the depth dims);
 //      2: Aggregator(skipna=True), either kind of id table (run-time)
-// The kernel's arguments field by field out of the kernel-argument segment (scalar loads; whole-struct copies through a word
-// pointer stay in scratch memory)
-__device__ __forceinline__ void load_args(S1Args& d, const_ptr<S1Args> s) {
-#pragma unroll
-  for (int i = 0; i < WBX_MAX_INPUTS; ++i) {
-    d.in[i] = s->in[i];
-    d.key_off[i] = s->key_off[i];
-    d.depth_off[i] = s->depth_off[i];
-    d.xstride[i] = s->xstride[i];
-  }
-  d.gk = s->gk, d.gd = s->gd, d.gtab = s->gtab, d.ngd = s->ngd;
-  d.nkey = s->nkey, d.D = s->D, d.nx = s->nx, d.dchunk = s->dchunk;
-  d.nchunk = s->nchunk, d.nxtile = s->nxtile, d.flags = s->flags;
-  d.out = s->out, d.xw = s->xw, d.M = s->M, d.mstride = s->mstride, d.lane = s->lane, d.ngd_t = s->ngd_t;
-}
-__device__ __forceinline__ void load_args(BinnedArgs& d, const_ptr<BinnedArgs> s) {  // (all but split_br: this kernel reads split_tab)
-  d.wt = s->wt, d.bits = s->bits, d.nBk = s->nBk, d.nBr = s->nBr, d.nj = s->nj;
-  d.nbin = s->nbin, d.nxt = s->nxt, d.nrs = s->nrs, d.rows_per_split = s->rows_per_split;
-  d.ncell = s->ncell, d.nblocks = s->nblocks, d.tmp = s->tmp, d.tmp_poison = s->tmp_poison, d.uni = s->uni;
-  d.aid = s->aid, d.aidm = s->aidm, d.words = s->words, d.nwords = s->nwords, d.atoms = s->atoms, d.order = s->order;
-  d.taper = s->taper, d.split_tab = s->split_tab;
-}
-__device__ __forceinline__ void load_args(EnsAtomsArgs& d, const_ptr<EnsAtomsArgs> s) {
-  d.wx = s->wx, d.wrow = s->wrow, d.tab = s->tab, d.part1 = s->part1, d.part2 = s->part2;
-  d.counters = s->counters, d.queue = s->queue, d.queue_next = s->queue_next, d.queue_static = s->queue_static, d.out = s->out, d.ng1 = s->ng1, d.ng2 = s->ng2;
-  d.masked = s->masked, d.twin_rows = s->twin_rows, d.out_mode = s->out_mode, d.accumulate = s->accumulate;
-  d.id_cell_rows = s->id_cell_rows, d.br_per_split = s->br_per_split, d.prof = s->prof;
-}
-
-// One patch, by one wave: (virtual) block `vb` of patch_grid<WPB>(g); lds_raw = the wave's staging slice.
+// One patch, by one wave: block `vb` of patch_grid<WPB>(g); lds_raw = the wave's staging slice.
 template <int MP, bool EXACT, bool NT, int MODE>
 __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArgs& g, const EnsAtomsArgs& e, uint32_t vb,
                                                 unsigned char* const lds_raw) {
   constexpr bool SKIPNA = MODE == 2;
-  constexpr int WPB = NT ? 1 : WBX_ENS_ATOMS_RAGGED_WPB;
+  constexpr int WPB = NT ? 1 : ENS_ATOMS_RAGGED_WPB;
   using Op = EnsOpF32<MP, EXACT, WBX_ENS_SORT>;
   constexpr int NQ = ENS_ATOMS_NQ, NOUT = ENS_ATOMS_NOUT;
-  constexpr int NLDS = MP < WBX_ENS_PIPE_NLDS ? MP : WBX_ENS_PIPE_NLDS;  // members staged through the LDS
+  constexpr int NLDS = MP < ENS_PIPE_NLDS ? MP : ENS_PIPE_NLDS;  // members staged through the LDS
   constexpr int NREG = MP - NLDS;                                        // members prefetched into VGPRs
   constexpr int NONE = 255;
   float(*stage)[64] = reinterpret_cast<float(*)[64]>(lds_raw);
@@ -213,7 +160,6 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
   const int64_t npatch = (int64_t)g.nrs * g.nxt;
   const int64_t patch = (int64_t)rs * g.nxt + xt;
   const int nw = g.nwords[bk * npatch + patch];
-  WBX_EA_STAMP(0);
   constexpr int TR = ENS_ATOMS_ROWS2;  // table rows per patch (the twin half is only touched in twin mode)
   const bool twin = SKIPNA || e.twin_rows != 0;
   double* const tab = e.tab + (cell * npatch + patch) * (TR * NQ);
@@ -382,27 +328,18 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
     }
   };
 
-  WBX_EA_STAMP(8);  // prologue done
   if (nrows > 0) {
     resolve_ahead();
     issue();
     resolve_ahead();
   }
-  WBX_EA_STAMP(9);  // first row asked for
   for (int i = 0; i < nrows; ++i) {
     typename Op::Regs r;
-#if WBX_ENS_ATOMS_ROW_BARRIER > 0
-    // (A/B, make ab-eabar*) the waves of a block -- adjacent x tiles of the same rows -- meet every few rows, so that the boundary
-    // lines two tiles share are asked for within the few microseconds a streamed line survives in the XCD's L2
+    // the waves of a block -- adjacent x tiles of the same rows -- meet every few rows (see ENS_ATOMS_ROW_BARRIER)
     if constexpr (WPB > 1) {
-      if ((i & (WBX_ENS_ATOMS_ROW_BARRIER - 1)) == 0) __builtin_amdgcn_s_barrier();
+      if ((i & (ENS_ATOMS_ROW_BARRIER - 1)) == 0) __builtin_amdgcn_s_barrier();
     }
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if WBX_EA_PROF
-    if (i == 0) WBX_EA_STAMP(10);  // first row has landed
-    if (i == 1) WBX_EA_STAMP(11);  // ... the second
-#endif
 #pragma unroll
     for (int m = 0; m < NLDS; ++m) r.xm[m] = (EXACT || m < M) ? stage[m][lane] : INFINITY;
 #pragma unroll
@@ -420,12 +357,7 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
     // no load of the next row is in flight here
     const unsigned long long m_ok = live_mask & __builtin_amdgcn_ballot_w64(id != NONE);
     unsigned long long n0 = __builtin_amdgcn_ballot_w64(id != c0), n1 = __builtin_amdgcn_ballot_w64(id != c1);
-#if WBX_EA_KNOCK >= 1  // timing diagnostic (wrong sums): every point goes to set 0 as atom 0, no hit / miss bookkeeping
-    c0 = 0;
-    n0 = 0ull;
-    n1 = ~0ull;
-#endif
-    if (WBX_EA_KNOCK == 0 && (m_ok & n0 & n1)) {  // wave-uniform: a lane meets an atom it is not accumulating
+    if (m_ok & n0 & n1) {  // wave-uniform: a lane meets an atom it is not accumulating
       const bool ok = __builtin_amdgcn_inverse_ballot_w64(m_ok);
       const bool miss = __builtin_amdgcn_inverse_ballot_w64(m_ok & n0 & n1);
       bool place = miss;
@@ -468,12 +400,7 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
       acc1[4] += w;
     }
   }
-  WBX_EA_STAMP(1);
   flush_all();
-  WBX_EA_STAMP(2);
-#if WBX_EA_KNOCK >= 2  // timing diagnostic: no sums over patches
-  return;
-#endif
 
   // ---- the patch is done: publish its table, then the sums over patches (see EnsAtomsArgs).  A record is [NOUT][64]: lane =
   // bin, so every lane of the wave adds the same six statistics and only the membership factor differs.
@@ -492,8 +419,7 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
   // sum of n consecutive records at src (index order); sc1 BUFFER loads: the compiler keeps a batch of them in flight, where
   // it waits for every atomic load on its own (16 records = 96 loads one after the other took 18 us of the kernel's tail)
   // (the number of lanes is a compile-time constant of each flavour: under the run-time `twin` test the loads of the upper six
-  //  lanes were issued and waited for one by one -- 192 of them in a level-2 sum: 28-100 us of a masked launch's tail,
-  //  tools/gpu_r4_ens_prof_mask.sh)
+  //  lanes were issued and waited for one by one -- 192 of them in a level-2 sum: 28-100 us of a masked launch's tail)
   auto add_records_n = [&](auto nl_tag, const double* src, int n, double (&sum)[NOUT2]) {
     constexpr int NL = decltype(nl_tag)::value;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(src), 0, 0x7fffffff, 0x00020000);
@@ -522,7 +448,6 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
   const int gn = npatch - k0 < ENS_ATOMS_G1 ? (int)(npatch - k0) : ENS_ATOMS_G1;
   uint32_t* const cnt1 = e.counters + cell * e.ng1 + g1;
   const bool last1 = last_of(cnt1, (uint32_t)gn);
-  WBX_EA_STAMP(3);
   if (!last1) return;
 
   // ---- level 1: atoms -> bins for the gn patches of the group.  Their tables and membership words go through the idle
@@ -595,7 +520,6 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
     for (int l = 0; l < NOUT2; ++l) sum[l] = __builtin_nan("");
   }
   put_record(e.part1 + (cell * e.ng1 + g1) * NP, sum);
-  WBX_EA_STAMP(4);
 
   // ---- level 2
   const int g2 = g1 / ENS_ATOMS_G2;
@@ -603,11 +527,9 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
   const int qn = e.ng1 - q0 < ENS_ATOMS_G2 ? e.ng1 - q0 : ENS_ATOMS_G2;
   uint32_t* const cnt2 = e.counters + (int64_t)g.ncell * e.ng1 + cell * e.ng2 + g2;
   const bool last2 = last_of(cnt2, (uint32_t)qn);
-  WBX_EA_STAMP(5);
   if (!last2) return;
   add_records(e.part1 + (cell * e.ng1 + q0) * NP, qn, sum);
   put_record(e.part2 + (cell * e.ng2 + g2) * NP, sum);
-  WBX_EA_STAMP(6);
 
   // ---- level 3: the cell's result
   uint32_t* const cnt3 = e.counters + (int64_t)g.ncell * (e.ng1 + e.ng2) + cell;
@@ -642,79 +564,20 @@ __device__ __forceinline__ void ens_atoms_patch(const S1Args& a, const BinnedArg
       }
     }
   }
-  WBX_EA_STAMP(7);
 }
 
-// PERSIST (r5; one-wave blocks): the launch is as many waves as the device holds at once (or fewer), and a wave that has
-// finished a patch draws the next one from a queue instead of exiting and leaving its slot to a new wave (2 800 of 3 072 slots
-// were occupied in the middle of a launch, profiles/r04_ens_atoms_phases.txt).  64 queues = (XCD y, eighth s of its patches):
-// ticket t of queue (y, s) is block 8 (8 t + s) + y of the plain launch, so an XCD still walks its contiguous eighth of the patches
-// in order; a wave's home queue is blockIdx & 63.  (One queue per XCD was 2 x SLOWER than the plain launch: atomics on one address
-// are served one after the other, ~100 ns each -- 5 000 draws per address and a departures counter that every wave hit once.
-// Now ~280 draws per address.)  A wave whose queue has run dry reads all 64 tickets with ONE load (lane = queue), prefers what is
-// left on its own XCD, and leaves when every queue is dry.  The tickets are not reset at the end (no departures counter): the
-// launches of a context alternate between two sets, and every launch clears the other one.
-template <int MP, bool EXACT, bool NT, int MODE = 0, bool PERSIST = false>
-__global__ void __launch_bounds__(64 * (NT ? 1 : WBX_ENS_ATOMS_RAGGED_WPB), WBX_ENS_PIPE_WAVES)
+// One wave per patch; a wave that has finished exits and leaves its slot to a new block.  Persistent waves that draw their
+// patches from ticket queues were measured SLOWER (profiles/r05_ens_atoms_persistent_ab.txt).
+template <int MP, bool EXACT, bool NT, int MODE = 0>
+__global__ void __launch_bounds__(64 * (NT ? 1 : ENS_ATOMS_RAGGED_WPB), ENS_PIPE_WAVES)
 ens_atoms_kernel(S1Args a, BinnedArgs g, EnsAtomsArgs e) {
-  constexpr int WPB = NT ? 1 : WBX_ENS_ATOMS_RAGGED_WPB;
-  constexpr int NLDS = MP < WBX_ENS_PIPE_NLDS ? MP : WBX_ENS_PIPE_NLDS;
+  constexpr int WPB = NT ? 1 : ENS_ATOMS_RAGGED_WPB;
+  constexpr int NLDS = MP < ENS_PIPE_NLDS ? MP : ENS_PIPE_NLDS;
   constexpr int NST = NLDS < 48 ? 48 : NLDS;  // (the level-1 finisher borrows 12 KB of it)
   __shared__ __attribute__((aligned(16))) unsigned char lds_all[WPB][NST * 256];
   const int wave_in_block = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
   unsigned char* const lds_raw = lds_all[wave_in_block];  // (every wave works in its own slice: no block-level sync anywhere)
-  if constexpr (!PERSIST) {
-    ens_atoms_patch<MP, EXACT, NT, MODE>(a, g, e, blockIdx.x, lds_raw);
-  } else {
-    static_assert(!PERSIST || WPB == 1, "persistent waves are one-wave blocks");
-    const int lane = threadIdx.x & 63;
-    if (blockIdx.x == 0) st_dev(e.queue_next + lane, 0u);
-    const uint32_t per_xcd = patch_per_xcd<WPB>(g);
-    const uint32_t home = blockIdx.x & 63u;
-    uint32_t q = home;
-    uint32_t static_round = 0;
-    const uint32_t mine_n = (per_xcd + 7u - ((uint32_t)lane >> 3)) >> 3;  // tickets of queue `lane`
-#pragma unroll 1
-    for (;;) {
-      uint32_t t = 0;
-      if (e.queue_static) {  // (A/B) no queue: block b takes the tickets b / 64, b / 64 + gridDim / 64, .. of queue b & 63
-        t = (blockIdx.x >> 6) + static_round * (gridDim.x >> 6);
-        ++static_round;
-        if (t >= ((per_xcd + 7u - (q >> 3)) >> 3)) break;
-      } else {
-        if (lane == 0) t = __hip_atomic_fetch_add(e.queue + q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-      }
-      if (t < ((per_xcd + 7u - (q >> 3)) >> 3)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staging slice is this patch's now
-        // The patch reads its arguments from the kernel-argument segment again (scalar loads through a pointer the compiler
-        // cannot see through): hoisted out of this loop, everything the prologue and the finish levels derive from them stays
-        // live across the sweep -- 154 spilled scalar and 21 spilled vector registers against 63 / 0 of the one-patch kernel.
-        const_ptr<char> kp = (const_ptr<char>)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(kp));
-        constexpr size_t off_g = (sizeof(S1Args) + alignof(BinnedArgs) - 1) / alignof(BinnedArgs) * alignof(BinnedArgs);
-        [[maybe_unused]] constexpr size_t off_e = (off_g + sizeof(BinnedArgs) + alignof(EnsAtomsArgs) - 1) / alignof(EnsAtomsArgs) * alignof(EnsAtomsArgs);
-#if WBX_EA_PERSIST_RELOAD
-        S1Args a2;
-        BinnedArgs g2;
-        EnsAtomsArgs e2;
-        load_args(a2, (const_ptr<S1Args>)kp);
-        load_args(g2, (const_ptr<BinnedArgs>)(kp + off_g));
-        load_args(e2, (const_ptr<EnsAtomsArgs>)(kp + off_e));
-        ens_atoms_patch<MP, EXACT, NT, MODE>(a2, g2, e2, ((t << 3) + (q >> 3)) * 8u + (q & 7u), lds_raw);
-#else
-        ens_atoms_patch<MP, EXACT, NT, MODE>(a, g, e, ((t << 3) + (q >> 3)) * 8u + (q & 7u), lds_raw);
-#endif
-        continue;
-      }
-      // dry: what is left anywhere?  (a queue seen non-empty may be dry by the time of the draw: then once more)
-      const uint32_t seen = ld_dev(e.queue + lane);
-      const unsigned long long left = __builtin_amdgcn_ballot_w64(seen < mine_n);
-      if (!left) break;
-      const unsigned long long near = left & (0x0101010101010101ull << (home & 7u));
-      q = (uint32_t)__builtin_ctzll(near ? near : left);
-    }
-  }
+  ens_atoms_patch<MP, EXACT, NT, MODE>(a, g, e, blockIdx.x, lds_raw);
 }
 #pragma clang diagnostic pop
 
@@ -735,7 +598,7 @@ inline bool ens_atoms_taper() {
 }
 
 inline int64_t ens_atoms_rows() {
-  static const int64_t rows = getenv("WBX_ENS_ATOMS_ROWS") && atol(getenv("WBX_ENS_ATOMS_ROWS")) > 0 ? atol(getenv("WBX_ENS_ATOMS_ROWS")) : WBX_ENS_ATOMS_ROWS;
+  static const int64_t rows = getenv("WBX_ENS_ATOMS_ROWS") && atol(getenv("WBX_ENS_ATOMS_ROWS")) > 0 ? atol(getenv("WBX_ENS_ATOMS_ROWS")) : ENS_ATOMS_ROWS;
   return rows;
 }
 
@@ -785,12 +648,10 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
   e.out = c.out;
   e.ng1 = ng1;
   e.ng2 = ng2;
-  if (int rc = ens_atoms_counters(ctx, (size_t)cells * (ng1 + ng2 + 1) + 128, &e.counters)) return rc;
-  e.queue = e.counters;  // (the two ticket sets sit at the head of the buffer: the same addresses whatever the geometry)
-  e.queue_next = e.counters + 64;
-  static const int static_env = getenv("WBX_ENS_ATOMS_STATIC") ? atoi(getenv("WBX_ENS_ATOMS_STATIC")) : 0;
-  e.queue_static = static_env;
-  e.counters += 128;
+  if (int rc = ens_atoms_counters(ctx, (size_t)cells * (ng1 + ng2 + 1), &e.counters)) return rc;
+  e.unused0 = e.unused2 = nullptr;
+  e.unused1 = 0;
+  e.unused3 = nullptr;
   e.masked = 0;
   e.twin_rows = twin ? 1 : 0;
   e.out_mode = skipna ? (twin_out ? 3 : 2) : (twin_out ? 1 : 0);
@@ -813,36 +674,10 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
   const bool ragged_lines = (plan->nx * plan->xstride[0] * 4) % 128 != 0 || plan->xstride[0] != 1;
   const bool nt = nt_env >= 0 ? nt_env != 0 : !ragged_lines;
   g.order = order_env >= 0 ? order_env : (ragged_lines ? 1 : 0);
-  const int64_t grid = nt ? patch_grid<1>(g) : patch_grid<WBX_ENS_ATOMS_RAGGED_WPB>(g);
-  e.prof = nullptr;
-#if WBX_EA_PROF
-  const size_t prof_bytes = (size_t)g.nblocks * 16 * sizeof(unsigned long long);
-  WBX_HIP(hipMalloc(reinterpret_cast<void**>(&e.prof), prof_bytes));
-  WBX_HIP(hipMemsetAsync(e.prof, 0, prof_bytes, ctx->stream));
-#endif
+  const int64_t grid = nt ? patch_grid<1>(g) : patch_grid<ENS_ATOMS_RAGGED_WPB>(g);
   const int mode = skipna ? 2 : (e.id_cell_rows ? 1 : 0);
-  const dim3 block(nt ? 64 : 64 * WBX_ENS_ATOMS_RAGGED_WPB);
+  const dim3 block(nt ? 64 : 64 * ENS_ATOMS_RAGGED_WPB);
 #define WBX_EA_LAUNCH(NTV, MODEV) hipLaunchKernelGGL((ens_atoms_kernel<MP, EXACT, NTV, MODEV>), dim3((unsigned)grid), block, 0, ctx->stream, a, g, e)
-#define WBX_EA_LAUNCH_P(MODEV) hipLaunchKernelGGL((ens_atoms_kernel<MP, EXACT, true, MODEV, true>), dim3((unsigned)pgrid), block, 0, ctx->stream, a, g, e)
-#if WBX_EA_PERSIST
-  // (diagnostic build, make ab-eapersist) one-wave blocks: persistent waves, as many as the device holds at once
-  // (WBX_ENS_ATOMS_PERSIST=0: one block per patch; = N > 1: N waves; WBX_ENS_ATOMS_STATIC=1: fixed shares instead of tickets)
-  static const int persist_env = getenv("WBX_ENS_ATOMS_PERSIST") ? atoi(getenv("WBX_ENS_ATOMS_PERSIST")) : 1;
-  const int64_t slots = (int64_t)ctx->num_cus * 4 * WBX_ENS_PIPE_WAVES / 8 * 8;
-  const bool persist = nt && persist_env != 0 && slots >= 8;
-  const int64_t pgrid = persist_env > 1 ? (grid < (int64_t)persist_env ? grid : (int64_t)persist_env / 8 * 8) : (grid < slots ? grid : slots);
-  if (persist) {
-    if (ctx->ens_queue_parity) {
-      uint32_t* const t = e.queue;
-      e.queue = e.queue_next;
-      e.queue_next = t;
-    }
-    ctx->ens_queue_parity ^= 1u;
-    if (mode == 0) WBX_EA_LAUNCH_P(0);
-    else if (mode == 1) WBX_EA_LAUNCH_P(1);
-    else WBX_EA_LAUNCH_P(2);
-  } else
-#endif
   if (nt) {
     if (mode == 0) WBX_EA_LAUNCH(true, 0);
     else if (mode == 1) WBX_EA_LAUNCH(true, 1);
@@ -853,25 +688,7 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
     else WBX_EA_LAUNCH(false, 2);
   }
 #undef WBX_EA_LAUNCH
-#undef WBX_EA_LAUNCH_P
   WBX_HIP(hipGetLastError());
-#if WBX_EA_PROF
-  {
-    WBX_HIP(hipStreamSynchronize(ctx->stream));
-    unsigned long long* host = (unsigned long long*)malloc(prof_bytes);
-    WBX_HIP(hipMemcpy(host, e.prof, prof_bytes, hipMemcpyDeviceToHost));
-    if (const char* path = getenv("WBX_EA_PROF_DUMP")) {
-      if (FILE* f = fopen(path, "wb")) {
-        const long long hdr[4] = {(long long)g.ncell, (long long)g.nrs, (long long)g.nxt, 16};
-        fwrite(hdr, sizeof(hdr), 1, f);
-        fwrite(host, 1, prof_bytes, f);
-        fclose(f);
-      }
-    }
-    free(host);
-    WBX_HIP(hipFree(e.prof));
-  }
-#endif
   return 0;
 }
 

@@ -18,29 +18,13 @@
 #include <cstdlib>
 
 #include "wbx_s1.hpp"
-#include "wbx_sortnet_gen.hpp"
 #include "wbx_sortnet3_gen.hpp"
 
-#ifndef WBX_ENS_MIN_WAVES
-#define WBX_ENS_MIN_WAVES 1  // no forced occupancy: 106 VGPRs / 4 waves per SIMD on its own since the fp64 divisions went (before: 140-155
-                             // VGPRs / 3 waves, and forcing 4 spilled 132 B: 0.63 ms vs 0.37 ms)
-#endif
-
-#ifndef WBX_ENS_MIN_WAVES_PLAIN
-#define WBX_ENS_MIN_WAVES_PLAIN WBX_ENS_MIN_WAVES  // the unmasked op alone (the masked / skipna wrappers keep WBX_ENS_MIN_WAVES)
-#endif
-#ifndef WBX_ENS_SORTNET3
-#define WBX_ENS_SORTNET3 1  // 0: Batcher's compare-exchange network for every size (A/B timing: make EXTRA=-DWBX_ENS_SORTNET3=0)
-#endif
-
-#ifndef WBX_ENS_NOFALLBACK
-#define WBX_ENS_NOFALLBACK 0  // diagnostic builds only
-#endif
-#ifndef WBX_ENS_STATS32
-#define WBX_ENS_STATS32 1  // 0: fp64 sums in the exact-M rank-form kernels too (A/B timing / exactness checks: make EXTRA=-DWBX_ENS_STATS32=0)
-#endif
-
 namespace wbx {
+
+// Minimum waves per SIMD the ensemble ops ask for: no forced occupancy -- 106 VGPRs / 4 waves per SIMD on its own since the fp64
+// divisions went (before: 140-155 VGPRs / 3 waves, and forcing 4 spilled 132 B: 0.63 ms vs 0.37 ms)
+constexpr int ENS_MIN_WAVES = 1;
 
 // not part of the ABI enum: stage-1 memory-pattern diagnostic used by tools/kbench.py (lane 0 = sum_m p - t)
 constexpr int WBX_ENS_DIAG_LOADONLY = 99;
@@ -126,7 +110,7 @@ struct EnsOpF32 {
   static constexpr int NIN = 2;
   static constexpr int NLANE = WBX_ENS_LANES;
   static constexpr int NACC = WBX_ENS_LANES;
-  static constexpr int XR_UNROLL = 1, XK_UNROLL = 1, MIN_WAVES = WBX_ENS_MIN_WAVES_PLAIN;
+  static constexpr int XR_UNROLL = 1, XK_UNROLL = 1, MIN_WAVES = ENS_MIN_WAVES;
 
   // One grid point's inputs in VGPRs.  load() only issues the (coalesced-across-lanes) member loads; compute() is
   // pure register work, so the skeleton can keep the NEXT point's loads in flight while this one is reduced.
@@ -151,7 +135,7 @@ struct EnsOpF32 {
   // The load-only diagnostic (WBX_ENS_DIAG_LOADONLY) streams the same 52 dword streams at 6.0 TB/s, so what is
   // left is VALU time (~2000 instructions per 64 points) that 3 waves/SIMD only partly overlap with the loads.
   // (r2) The network itself: Batcher's 415 compare-exchanges (830 instructions) -> 54 compare-exchanges + 166 3-sorters (606):
-  // 0.349 -> 0.316 ms on one box (tools/gpu_ens_ab.sh), 133 VGPRs / 3 waves per SIMD; forcing 4 waves (5 spilled registers)
+  // 0.349 -> 0.316 ms on one box (profiles/r02_ens_sortnet_ab.txt), 133 VGPRs / 3 waves per SIMD; forcing 4 waves (5 spilled registers)
   // changes nothing.  A wave-uniform row base + one 32-bit VGPR offset for all 52 streams (to drop the 53 v_lshl_add_u64 per
   // point): the compiler reassociates the sum back into 64-bit VGPR addresses, 107 VGPRs, 0.329 against 0.312 ms -- not kept.
   __device__ __forceinline__ static void load(const S1Args& a, const int64_t (&ro)[WBX_MAX_INPUTS], int64_t x, Regs& r) {
@@ -267,29 +251,26 @@ struct EnsOpF32 {
         asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(u), "v"(v));
         return r;
       };
-      if constexpr (WBX_ENS_SORTNET3) {
-        // merge sort of compare-exchanges and 3-sorters (gen_sortnet3.py): v_min3 / v_med3 / v_max3 cost what v_min / v_max
-        // do, so M = 51 sorts in 606 instructions instead of the 830 of Batcher's 415 comparators (32: 301 / 382, 64: 850 / 1086)
-        SortNet3<MP>::sort(
-            xm, mn, mx,
-            [](float u, float v, float w) {
-              float r;
-              asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
-              return r;
-            },
-            [](float u, float v, float w) {
-              float r;
-              asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
-              return r;
-            },
-            [](float u, float v, float w) {
-              float r;
-              asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
-              return r;
-            });
-      } else {
-        SortNet<MP>::sort(xm, mn, mx);
-      }
+      // merge sort of compare-exchanges and 3-sorters (gen_sortnet3.py): v_min3 / v_med3 / v_max3 cost what v_min / v_max
+      // do, so M = 51 sorts in 606 instructions instead of the 830 of Batcher's 415 comparators (32: 301 / 382, 64: 850 / 1086;
+      // profiles/r02_ens_sortnet_ab.txt)
+      SortNet3<MP>::sort(
+          xm, mn, mx,
+          [](float u, float v, float w) {
+            float r;
+            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
+            return r;
+          },
+          [](float u, float v, float w) {
+            float r;
+            asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
+            return r;
+          },
+          [](float u, float v, float w) {
+            float r;
+            asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "v"(v), "v"(w));
+            return r;
+          });
     }
 
     bool redo = false;
@@ -301,7 +282,7 @@ struct EnsOpF32 {
       r.poison = 0.f;
       return weird;  // per lane: the caller redoes such a point with the generic operator
     }
-    if constexpr (FAST32 && EXACT && ALGO == WBX_ENS_SORT && WBX_ENS_STATS32) {
+    if constexpr (FAST32 && EXACT && ALGO == WBX_ENS_SORT) {
       // the hot instantiations (M = 50 / 51, rank form): fp32 chain sums on median-centred members (stats32), unless a lane
       // of the wave holds a point whose magnitudes could overflow / underflow an fp32 square or sum.  Then the CALLER redoes
       // the point with the generic fp64 op (members re-read from memory, a rolled loop: no registers of the hot path are
@@ -310,7 +291,7 @@ struct EnsOpF32 {
       const float range = xm[MP - 1] - xm[0];
       const float big = fmaxf(fmaxf(fabsf(xm[0]), fabsf(xm[MP - 1])), fabsf(r.t));
       const bool fast_ok = (range == 0.f || (range >= 0x1p-50f && range <= 0x1p60f)) && big <= 0x1p100f;
-      redo = !WBX_ENS_NOFALLBACK && __builtin_amdgcn_ballot_w64(!fast_ok) != 0;
+      redo = __builtin_amdgcn_ballot_w64(!fast_ok) != 0;
       if (!redo) stats32(a, xm, r.t, poison, val);
       r.poison = poison;
     } else {
@@ -550,7 +531,7 @@ struct EnsMasked {
   static constexpr int NIN = Core::NIN;
   static constexpr int NLANE = Core::NLANE;
   static constexpr int NACC = Core::NLANE + (SKIPNA ? Core::NLANE : 1);  // same count-lane convention as DetOp
-  static constexpr int XR_UNROLL = 1, XK_UNROLL = 1, MIN_WAVES = WBX_ENS_MIN_WAVES;
+  static constexpr int XR_UNROLL = 1, XK_UNROLL = 1, MIN_WAVES = ENS_MIN_WAVES;
 
   __device__ __forceinline__ static void values(const S1Args& a, const int64_t (&ro)[WBX_MAX_INPUTS], int64_t x,
                                                 double (&val)[NLANE]) {
@@ -606,25 +587,19 @@ struct EnsMasked {
 // w[e mod nx] comes from the fp64 table in global memory (5.7 KB, cache resident), fetched one tile ahead like the target.
 // (A first version of this flavour lost to s1_xf1_kernel in round 3 -- 1.48-1.52 against 1.44 ms for the 37-level field --
 // because both started their lanes one trip ahead instead of dropping them: 12 % more line requests, see wbx_s1.hpp.)
-#ifndef WBX_ENS_PIPE_NLDS
-#define WBX_ENS_PIPE_NLDS 50   // members staged through the LDS (x 256 B per one-wave block)
-#endif
-#ifndef WBX_ENS_PIPE_WAVES
-#define WBX_ENS_PIPE_WAVES 3   // waves per SIMD the register budget is cut for (12 800-byte blocks: 12 per CU)
-#endif
+constexpr int ENS_PIPE_NLDS = 50;   // members staged through the LDS (x 256 B per one-wave block)
+constexpr int ENS_PIPE_WAVES = 3;   // waves per SIMD the register budget is cut for (12 800-byte blocks: 12 per CU)
 // (the skipna_ensemble flavour -- per-lane member counts, fp64 sums over the valid members -- needed 209 registers = two waves per
 //  SIMD while its sums selected and weighted every member in fp64 by the per-lane count; with stats_skipna's compile-time
 //  coefficients it is 151 registers and runs three: 0.423 -> 0.378 ms on the 1.73 GB variable, 51 -> 57 % of the HBM peak; with the
 //  missing members replaced by the shift itself -- no per-member select, no class tests -- 113 registers, 0.336 ms = 64 %)
-#ifndef WBX_ENS_PIPE_SKIPNA_WAVES
-#define WBX_ENS_PIPE_SKIPNA_WAVES 3
-#endif
+constexpr int ENS_PIPE_SKIPNA_WAVES = 3;
 template <int MP, bool EXACT, int ALGO, bool FLAT>
-__global__ void __launch_bounds__(64, ALGO == WBX_ENS_SKIPNA_SORT ? WBX_ENS_PIPE_SKIPNA_WAVES : WBX_ENS_PIPE_WAVES)
+__global__ void __launch_bounds__(64, ALGO == WBX_ENS_SKIPNA_SORT ? ENS_PIPE_SKIPNA_WAVES : ENS_PIPE_WAVES)
 ens_pipe_kernel(S1Args a, int R) {
   using Op = EnsOpF32<MP, EXACT, ALGO>;
   constexpr int NA = Op::NACC;
-  constexpr int NLDS = MP < WBX_ENS_PIPE_NLDS ? MP : WBX_ENS_PIPE_NLDS;  // members staged through the LDS
+  constexpr int NLDS = MP < ENS_PIPE_NLDS ? MP : ENS_PIPE_NLDS;  // members staged through the LDS
   constexpr int NREG = MP - NLDS;          // members prefetched into VGPRs
   __shared__ float stage[NLDS][64];
   const int lane = threadIdx.x;

@@ -360,14 +360,7 @@ inline int patch_finish(wbx_ctx* ctx, const BinnedArgs& g, int nacc, double* out
 // The waves are independent (own slots, own sweeps) but start together and walk the same rows, so a row's WPB x 256 B
 // are requested at about the same time.  (Tried for DRAM page locality with WPB = 4; measured slower than lone waves,
 // see wbx_det_binned.hip -- both patch kernels run WPB = 1.)  grid = patch_grid<WPB>(g).
-// blocks per XCD of patch_grid<WPB>(g): the tickets of a persistent kernel's per-XCD queue (ens_atoms_kernel)
-template <int WPB>
-__device__ __forceinline__ uint32_t patch_per_xcd(const BinnedArgs& g) {
-  const uint32_t nxq = ((uint32_t)g.nxt + WPB - 1) / WPB;
-  return ((uint32_t)g.ncell * nxq * (uint32_t)g.nrs + 7u) >> 3;
-}
-
-// `vb`: the block index to decode -- blockIdx.x, or the virtual one a persistent wave drew from a queue
+// `vb`: the block index to decode (blockIdx.x)
 template <int WPB>
 __device__ __forceinline__ bool patch_decode(const BinnedArgs& g, int64_t& cell, int& xt, int& rs, uint32_t vb) {
   // 32-bit arithmetic (the launcher checks nblocks < 2^31): a 64-bit divide is a ~100-instruction sequence on this ISA,

@@ -566,13 +566,10 @@ __device__ __forceinline__ C2 ld_c2(const v4* p) {
 }
 __device__ __forceinline__ void st_c2(v4* p, C2 a) { *p = (v4){a.re.x, a.re.y, a.im.x, a.im.y}; }
 
-// WBX_SPECTRUM_DEMEAN (what it is for: wbx_zspec1440.hpp): rows are shifted by an estimate of their mean in front of the fp32
+// The mean shift (what it is for: wbx_zspec1440.hpp): rows are shifted by an estimate of their mean in front of the fp32
 // transform and F_0 is restored in fp64 -- the 1440-point kernels, and the one-wave teams (G == 64: rows of up to 256 points,
 // i.e. the 64- and 240-point grids of the public configs) of the generic kernel below, where the team's mean is one DPP
 // reduction; teams of two or four waves (257..2048-point rows other than 1440) transform the rows as they are.
-#ifndef WBX_SPECTRUM_DEMEAN
-#define WBX_SPECTRUM_DEMEAN 1
-#endif
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_moved_f32(float v) {
@@ -668,7 +665,7 @@ __device__ __forceinline__ v2 team_total_f32(v2 s, v4* buf, int tid) {
 // a read, and an N-way bank conflict multiplies that), so the strided side is the read.  ns shrinks from n2 / R to 1.
 // FIRST (ns == nb): the inputs k + t * nb are taken straight from the two rows in global memory (coalesced), the raw
 // rows never visit the LDS.  All LDS reads precede all writes.
-// FIRST with WBX_SPECTRUM_DEMEAN: the rows are shifted by the mean of their even points (the real parts of the packed row:
+// FIRST: the rows are shifted by the mean of their even points (the real parts of the packed row:
 // every one of them is in some thread's registers here; teams of 2 / 4 waves add their wave sums through the LDS,
 // team_total_f32) before the first butterfly; the shift comes back in *msh for the k = 0 term of the unpack.
 template <int R, int NB, int G, bool FIRST>
@@ -702,7 +699,7 @@ __device__ __forceinline__ void team_pass(v4* __restrict__ buf, const float2* __
       }
     }
   }
-  if constexpr (FIRST && WBX_SPECTRUM_DEMEAN) {
+  if constexpr (FIRST) {
     v2 sum = {0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -862,24 +859,22 @@ __global__ void __launch_bounds__(256) zspec_fused_kernel(const float* __restric
     const int32_t ga = group[r], gb = two ? group[r + 1] : ga;
     const v2* rowa = reinterpret_cast<const v2*>(field + r * row_stride);
     const v2* rowb = reinterpret_cast<const v2*>(field + (two ? r + 1 : r) * row_stride);
-    v2 msh = {0.f, 0.f};  // the shift of rows A and B (WBX_SPECTRUM_DEMEAN), team-uniform
+    v2 msh = {0.f, 0.f};  // the shift of rows A and B, team-uniform
     if constexpr (R0 > 0) {
       C2 v[RP];
 #pragma unroll
       for (int t = 0; t < RP; ++t) v[t] = {{pa[t].x, two ? pb[t].x : 0.f}, {pa[t].y, two ? pb[t].y : 0.f}};
       if (r + 2 < r1) fetch(r + 2);
-      if constexpr (WBX_SPECTRUM_DEMEAN) {  // the rows shifted by the mean of their even points, as in team_pass
-        v2 sum = {0.f, 0.f};
-        if (tid < nb0) {
+      v2 sum = {0.f, 0.f};  // the rows shifted by the mean of their even points, as in team_pass
+      if (tid < nb0) {
 #pragma unroll
-          for (int t = 0; t < RP; ++t) sum += v[t].re;
-        }
-        msh = team_total_f32<G>(sum, buf, tid) * (1.0f / (float)n2);
+        for (int t = 0; t < RP; ++t) sum += v[t].re;
+      }
+      msh = team_total_f32<G>(sum, buf, tid) * (1.0f / (float)n2);
 #pragma unroll
-        for (int t = 0; t < RP; ++t) {
-          v[t].re -= msh;
-          v[t].im -= msh;
-        }
+      for (int t = 0; t < RP; ++t) {
+        v[t].re -= msh;
+        v[t].im -= msh;
       }
       if (tid < nb0) {
         butterfly<RP>(v);
@@ -917,12 +912,10 @@ __global__ void __launch_bounds__(256) zspec_fused_kernel(const float* __restric
         const C2 x = cadd(e, wo), xm = csub(e, wo);
         const v2 p = norm2(x), pm = norm2(xm);  // (row A, row B)
         double pxd = (double)p.x, pyd = (double)p.y;
-        if constexpr (WBX_SPECTRUM_DEMEAN) {
-          if (k == 0) {  // x.re = F'_0 of the shifted rows, x.im = 0: F_0 = F'_0 + n m, formed and squared in fp64
-            const double fa = (double)x.re.x + (double)fs.n * (double)msh.x, fb = (double)x.re.y + (double)fs.n * (double)msh.y;
-            pxd = fa * fa;
-            pyd = fb * fb;
-          }
+        if (k == 0) {  // x.re = F'_0 of the shifted rows, x.im = 0: F_0 = F'_0 + n m, formed and squared in fp64
+          const double fa = (double)x.re.x + (double)fs.n * (double)msh.x, fb = (double)x.re.y + (double)fs.n * (double)msh.y;
+          pxd = fa * fa;
+          pyd = fb * fb;
         }
         const bool mirror = km != k;
         if (split) {
@@ -985,9 +978,7 @@ static const char* spectrum_prof_path() { return nullptr; }
 
 // Launches zspec1440_kernel: as many one-wave teams per block as the LDS holds (12: tables + 12 x 11.4 KB), one block per
 // CU, and -- every team takes the same time -- a grid of exactly `rounds` resident sets.
-#ifndef WBX_SPECTRUM_SKEW_DEFAULT
-#define WBX_SPECTRUM_SKEW_DEFAULT 100  // per mille of a team's rows (WBX_SPECTRUM_SKEW overrides; 0 / 40 / 70 / 100 / 130 / 200 / 250: 0.249 / 0.245 / 0.242 / 0.239 / 0.241 / 0.242 / 0.248 ms)
-#endif
+constexpr int SPECTRUM_SKEW_DEFAULT = 100;  // per mille of a team's rows (WBX_SPECTRUM_SKEW overrides; 0 / 40 / 70 / 100 / 130 / 200 / 250: 0.249 / 0.245 / 0.242 / 0.239 / 0.241 / 0.242 / 0.248 ms)
 
 static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t row_stride, int64_t nrows,
                        const int32_t* group, const double* scale, double* power_out, int32_t ngroup, int32_t accumulate) {
@@ -1021,7 +1012,7 @@ static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t r
   teams = (nrows + rows_per_team - 1) / rows_per_team;
   const unsigned blocks = (unsigned)((teams + nteam - 1) / nteam);
   // rows the oldest four waves of a block take more / the youngest four less (whole pairs), see the kernel
-  static const int skew_permille = getenv("WBX_SPECTRUM_SKEW") ? atoi(getenv("WBX_SPECTRUM_SKEW")) : WBX_SPECTRUM_SKEW_DEFAULT;
+  static const int skew_permille = getenv("WBX_SPECTRUM_SKEW") ? atoi(getenv("WBX_SPECTRUM_SKEW")) : SPECTRUM_SKEW_DEFAULT;
   int skew = 0;
   if (nteam == 12 && rows_per_team >= 16) skew = 2 * (int)(((int64_t)rows_per_team * skew_permille + 1000) / 2000);
   if (skew >= rows_per_team) skew = 0;
@@ -1076,9 +1067,7 @@ static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t r
 }
 
 // Launches zspec1440_latfast_kernel over nslab slabs of rps adjacent rows (row_stride 1, longitude strided).
-#ifndef WBX_SPECTRUM_LF_PRIO_DEFAULT
-#define WBX_SPECTRUM_LF_PRIO_DEFAULT 1  // (0 / 1 / 2: 0.3673 / 0.3630 / 0.3674 ms back to back on one box) user priority of a block's waves by age (WBX_SPECTRUM_LF_PRIO overrides), see the kernel
-#endif
+constexpr int SPECTRUM_LF_PRIO_DEFAULT = 1;  // (0 / 1 / 2: 0.3673 / 0.3630 / 0.3674 ms back to back on one box) user priority of a block's waves by age (WBX_SPECTRUM_LF_PRIO overrides), see the kernel
 
 static int launch_1440_latfast(wbx_ctx* ctx, FftState* st, const float* field, int64_t lon_stride, const int64_t* d_slab_off,
                                int64_t rps, int64_t nslab, const int32_t* group, const double* scale, double* power_out,
@@ -1108,7 +1097,7 @@ static int launch_1440_latfast(wbx_ctx* ctx, FftState* st, const float* field, i
   // algorithmic against 1.09 x for 33: the shared lines are found in L2 either way)
   int64_t runs = (rps + 21) / 22;
   if (const char* e = getenv("WBX_SPECTRUM_LF_RUNS")) runs = atoi(e) >= (rps + Z14_RUN - 1) / Z14_RUN ? atoi(e) : runs;  // A/B timing
-  static const int lf_prio = getenv("WBX_SPECTRUM_LF_PRIO") ? atoi(getenv("WBX_SPECTRUM_LF_PRIO")) : WBX_SPECTRUM_LF_PRIO_DEFAULT;
+  static const int lf_prio = getenv("WBX_SPECTRUM_LF_PRIO") ? atoi(getenv("WBX_SPECTRUM_LF_PRIO")) : SPECTRUM_LF_PRIO_DEFAULT;
   const int64_t per_xcd = ((nslab + 7) / 8) * runs;  // (slab, run) pairs of the busiest XCD
   if (per_xcd < nlocal) nlocal = (int)per_xcd;
   // the records of this launch: the block's table goes out when the step's group differs from the last one's (at most once per
@@ -1386,8 +1375,7 @@ static int launch_1440_det(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, 
   a.in[1] = t;
   a.in[2] = c;
   a.out = partial_out;
-  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)ZD_TEAMS * Z14_BUF * sizeof(v4) +
-                     ((has_c && !WBX_ZD_C_IN_REGISTERS) ? (size_t)ZD_TEAMS * 24 * 64 * sizeof(float) : 0);  // + the climatology staging slots
+  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)ZD_TEAMS * Z14_BUF * sizeof(v4);
   const void* fn = fold ? (has_c ? reinterpret_cast<const void*>(&zspec1440_det_kernel<true, true>) : reinterpret_cast<const void*>(&zspec1440_det_kernel<false, true>))
                         : (has_c ? reinterpret_cast<const void*>(&zspec1440_det_kernel<true>) : reinterpret_cast<const void*>(&zspec1440_det_kernel<false>));
   int& per_cu = st->occupancy[std::make_pair(fn, lds)];
@@ -1443,7 +1431,7 @@ static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan
   a.in[1] = t;
   a.in[2] = c;
   a.out = partial_out;
-  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)ZL_TEAMS * WBX_ZL_BUFL * sizeof(v4) +
+  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)ZL_TEAMS * ZL_BUFL * sizeof(v4) +
                      (size_t)2 * (Z14_N2 + 2) * sizeof(double) + (size_t)ZL_GROUPS * 4 * 2 * 6 * sizeof(double);
   const void* fn = has_c ? reinterpret_cast<const void*>(&zspec1440_det_latfast_kernel<true>)
                          : reinterpret_cast<const void*>(&zspec1440_det_latfast_kernel<false>);

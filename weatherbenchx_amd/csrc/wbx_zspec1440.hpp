@@ -31,11 +31,11 @@ constexpr int Z14_TABLES = Z14_TW1 + Z14_TW2 + Z14_TWR;
 // The transform is fp32: every output carries ~eps |F|_max of its row, and on a physical field |F|_max is the mean (F_0 = n x
 // mean: T ~ 280 K against anomalies of a few K, geopotential 5e4 against 1e2..1e3), so the wavenumbers above it were held to
 // eps x mean / anomaly instead of eps (measured on N(280, 1) rows: median relative error of S_k 1.0e-5 per row, up to 48 % on
-// single coefficients, against 1.4e-7 on N(0, 1) rows).  With WBX_SPECTRUM_DEMEAN a row is shifted by m = an estimate of its
+// single coefficients, against 1.4e-7 on N(0, 1) rows).  So a row is shifted by m = an estimate of its
 // mean (fp32; any m is valid, it only has to be close) before the transform (z14_demean) -- x - m is exact in fp32 for x
 // within a factor two of m -- which changes nothing but F_0 (n is even: the Nyquist term keeps its value), and
 // F_0 = F'_0 + n m is put back in fp64 where |X_0|^2 is formed (z14_pair).
-// (the macro and the DPP reduction: wbx_spectrum.hip, in front of the generic kernel, whose one-wave teams use them too)
+// (the DPP reduction: wbx_spectrum.hip, in front of the generic kernel, whose one-wave teams use them too)
 
 // -> (m_A, m_B) of the rows A and B whose pass-1 inputs v holds; subtracted from v in place.  Every instruction here is
 // paid three times per SIMD (its waves run the passes in step), so the estimate takes what is cheap: the real parts of every
@@ -45,7 +45,6 @@ constexpr int Z14_TABLES = Z14_TW1 + Z14_TW2 + Z14_TWR;
 // antipodal arcs of 32 degrees, 128 samples -- so that the reduction runs under the latency of the other ten loads.
 template <bool FEW = false>
 __device__ __forceinline__ v2 z14_demean(C2 (&v)[12]) {
-  if constexpr (!WBX_SPECTRUM_DEMEAN) return (v2){0.f, 0.f};
   v2 s = v[0].re + v[6].re;
   if constexpr (!FEW) {
 #pragma unroll
@@ -145,14 +144,14 @@ __device__ __forceinline__ void z14_send(double* out, const Z14Lane& c, const do
 // the pass-1 stores.)
 // PT (wbx_zspec_det.hpp): rows A and B are the predictions' and the targets' row of ONE location; B's sums go to their own
 // accumulators accb / accmb instead of joining A's (no `split` then).
-// TW_EARLY (r6; 1 in the fused det + spectra sweep): the lane's twiddles of a stage (and the unpack's mirror partners) are ASKED FOR
+// TW_EARLY (r6; the fused det + spectra sweep): the lane's twiddles of a stage (and the unpack's mirror partners) are ASKED FOR
 // ahead of the arithmetic in front of their use -- left alone the compiler reads them from the LDS just in time, two or three at a
 // stretch, each stretch behind its own `s_waitcnt lgkmcnt(0)` (~30 waits per row; with the reads grouped ~12): -1 % at unchanged
 // registers (profiles/r06_det_spectrum_twearly_ab.txt).  The first attempt changed the last fp32 bit of the sweep's spectra -- the
 // other source shape made the compiler fuse other products with their sums -- until the ambiguous sums were pinned (`prod`,
-// wbx_spectrum.hip): with them the plain kernel (TW_EARLY = 0: no registers for the grouping at three waves per SIMD) and the sweep
+// wbx_spectrum.hip): with them the plain kernel (TW_EARLY = false: no registers for the grouping at three waves per SIMD) and the sweep
 // return the same bits again, whatever their schedules.
-template <int KNOCK, bool PT = false, int TW_EARLY = 0, typename At>
+template <int KNOCK, bool PT = false, bool TW_EARLY = false, typename At>
 __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c, const float2* __restrict__ tw1,
                                          const float2* __restrict__ twr, double sca, double scb, bool split, int32_t gb,
                                          double (&acc)[6], double (&accm)[6], double* __restrict__ power, At&& at,
@@ -164,7 +163,7 @@ __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c,
     float2 w[11];
 #pragma unroll
     for (int k1 = 1; k1 < 12; ++k1) w[k1 - 1] = tw1[(k1 - 1) * 60 + L];
-    if constexpr (TW_EARLY == 1) __builtin_amdgcn_sched_barrier(0);  // the eleven reads are issued here ...
+    __builtin_amdgcn_sched_barrier(0);  // the eleven reads are issued here ...
     dft12(v);
 #pragma unroll
     for (int k1 = 1; k1 < 12; ++k1) v[k1] = ctw(v[k1], w[k1 - 1]);  // ... and waited for once, here
@@ -191,7 +190,7 @@ __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c,
 #pragma unroll
       for (int q = 1; q < 5; ++q) w5[i][q - 1] = c.tw5[4 * i + 12 * (q - 1)];
     }
-    if constexpr (TW_EARLY == 1) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();  // every load of the first layout precedes the stores of the second
   at(1);
@@ -232,7 +231,7 @@ __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c,
       zm[s] = ld_c2(s == 0 ? buf + c.mir0 : buf + (Z14_N2 - 60 * s) - L);
       wu[s] = twr[s == 0 ? c.k0 : L + 60 * s];
     }
-    if constexpr (TW_EARLY == 1) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int s = 0; s < 6; ++s) {
@@ -251,7 +250,7 @@ __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c,
     const v2 p = (KNOCK & 8) ? x.re : norm2(x);     // (row A, row B) of k
     const v2 pm = (KNOCK & 8) ? xm.re : norm2(xm);  // ... of 720 - k
     double pxd = (double)p.x, pyd = (double)p.y;
-    if constexpr (WBX_SPECTRUM_DEMEAN && !(KNOCK & 8)) {
+    if constexpr (!(KNOCK & 8)) {
       // k = 0 (lane 0, s = 0): x.re = 2 F'_0 of the shifted rows and x.im = 0 exactly; F_0 = F'_0 + n m (2 F_0 here: E and O
       // are used without their factor 1/2), formed and squared in fp64 -- the mean is not squeezed through fp32 again
       if (s == 0 && c.lane == 0) {
@@ -295,10 +294,8 @@ __device__ __forceinline__ void z14_pair(C2 (&v)[12], v4* buf, const Z14Lane& c,
 // KNOCK (diagnostic, wrong results; tools/kbench_spectrum_raw.py): 1 = every pair re-reads the team's first rows (L2 hits,
 // no HBM stream), 2 = the LDS stores of the three exchanges are dropped, 4 = their loads too, 8 = no unpack arithmetic.
 // FETCH_EARLY (A/B): the next pair's 24 loads in front of pass 1 instead of behind its stores (0.285 vs 0.275 ms per field)
-#ifndef WBX_Z14_TW_EARLY
-#define WBX_Z14_TW_EARLY 0  // z14_pair<.., TW_EARLY> in the three-wave spectrum kernel (1: +45 %, 116 B of scratch; 2 = the source shape without the
-                            // scheduling barriers: the same)
-#endif
+// z14_pair<.., TW_EARLY = false>: grouping the LDS reads costs this three-wave kernel +45 % and 116 B of scratch
+// (profiles/r06_det_spectrum_twearly_ab.txt)
 template <bool PROF, int KNOCK, bool ROTATE = true, bool FETCH_EARLY = false>
 __global__ void __launch_bounds__(768) zspec1440_kernel(const float* __restrict__ field, int64_t row_stride, int64_t nrows,
                                                         int rows_per_team, int skew, const float2* __restrict__ tables_g,
@@ -406,7 +403,7 @@ __global__ void __launch_bounds__(768) zspec1440_kernel(const float* __restrict_
     if (ga != cur) flush(ga);  // wave-uniform
     // stamps (PROF): 1 -> 2 pass 1 | 2 -> 3 transpose 1 round trip (stores drain, 15 loads return) | 3 -> 4 pass 2 |
     // 4 -> 5 transpose 2 round trip | 5 -> 6 pass 3 | 6 -> 7 mirror exchange + unpack + fp64 sums
-    z14_pair<(KNOCK & 14), false, WBX_Z14_TW_EARLY>(v, buf, c, tw1, twr, sca, scb, false, ga, acc, accm, nullptr,
+    z14_pair<(KNOCK & 14), false, false>(v, buf, c, tw1, twr, sca, scb, false, ga, acc, accm, nullptr,
                            [&](int i) {
                              mark(i + 2, i == 1 || i == 3 || i == 5);
                              if constexpr (!FETCH_EARLY) {  // the registers of pass 1's inputs are free: the next pair's loads

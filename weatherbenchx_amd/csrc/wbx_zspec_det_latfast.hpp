@@ -31,9 +31,7 @@ constexpr int ZL_TEAMS = 8;                                // teams = rows of a 
 constexpr int ZL_THREADS = 64 * ZL_TEAMS;
 constexpr int ZL_ITEMS = 12;                               // longitudes per loader: j0 + 128 n (n = 11: j0 < 32 only)
 constexpr int ZL_GROUPS = ZL_THREADS / 16;                 // DPP rows of the block: 32, each with four lanes per row pair
-#ifndef WBX_ZL_BUFL
-#define WBX_ZL_BUFL 732                                    // v4 elements between the team buffers (>= Z14_BUF; = 4 mod 8: the staging stores of a wave -- four row pairs x 16 longitudes -- then fall on all 64 banks twice)
-#endif
+constexpr int ZL_BUFL = 732;                               // v4 elements between the team buffers (>= Z14_BUF; = 4 mod 8: the staging stores of a wave -- four row pairs x 16 longitudes -- then fall on all 64 banks twice)
 
 // KNOCK (diagnostic instantiations, wrong results; WBX_ZL_KNOCK): 1 = no deterministic arithmetic, 2 = no passes, 4 = no global
 // loads, 8 = no staging stores
@@ -44,7 +42,7 @@ __global__ void __launch_bounds__(ZL_THREADS) zspec1440_det_latfast_kernel(
   __shared__ int team_in_table[ZL_TEAMS];   // the team's sums of the last step sit in its buffer, for the block's tables
   constexpr int NA = HAS_C ? 6 : 3;
   constexpr int NIN = HAS_C ? 3 : 2;
-  constexpr int BUFL = WBX_ZL_BUFL;
+  constexpr int BUFL = ZL_BUFL;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   float2* const tw1 = reinterpret_cast<float2*>(lds_raw);
   float2* const tw2 = tw1 + Z14_TW1;
