@@ -318,6 +318,33 @@ int wbx_cat_exceed_field(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype, int n
                          const void* p, const void* t, const double* threshold_field, int64_t category_stride,
                          const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: thresholded 2x2 contingency tables (joined ABI 13) -------------------------------------------
+ * The four cells of the contingency table of a forecast and an observation at `nthr` thresholds, i.e. TruePositives /
+ * FalsePositives / FalseNegatives / TrueNegatives (categorical.py:25-101) of inputs binarised by ContinuousToBinary
+ * (wrappers.py:50-88), in one pass over p and t.  Per point and threshold k:
+ *     P_k = (double)p > thresholds[k],  O_k = (double)t > thresholds[k]      (strict, on the threshold as given)
+ *     TP = P_k & O_k,  FP = P_k & !O_k,  FN = !P_k & O_k,  TN = !P_k & !O_k  -- exactly one of them is 1
+ * A comparison with a NaN threshold is false (the point counts as TN -- unlike WBX_CAT_EXCEED, where it is NaN);
+ * -0.0 > 0.0 is false; +inf exceeds every finite threshold.  A point whose p or t is NaN is a NaN statistic in all
+ * 4 * nthr lanes: without flags it poisons every value lane of its partial; under WBX_FLAG_MASKED alone it contributes
+ * exactly 0 where the mask is 0 and poisons where it is not; under WBX_FLAG_SKIPNA it is counted out.
+ * Lane order is part of the ABI: value lane cell * nthr + k, cell in (TP, FP, FN, TN).  Count lanes follow the library's
+ * convention (none / one shared / one per value lane); under SKIPNA all 4 * nthr of them are equal (the number of valid,
+ * non-NaN points).  partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial: wbx_s1_partial_len with
+ * lanes = 4 * nthr, wbx_contract and wbx_contract_bits serve it unchanged.  Every output is an integer count < 2^32 held
+ * in fp64 (or NaN): the result is a function of the inputs and the plan only, bit for bit.
+ * `thresholds` is a DEVICE float64[nthr].  float32 inputs are compared in float32 against the threshold rounded toward
+ * -inf to float32, which decides exactly like the float64 comparison for every float32 value (+-inf and thresholds
+ * beyond the float32 range included; rounding to nearest would not: float(0.1) > 0.1).
+ * plan: flags within MASKED | SKIPNA, plane_rows = 0, no x_weights; vec = 4 is honoured where x is summed (x kept: one x
+ * per lane); depth_chunk * nx < 2^32 (the counters are uint32).  nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero
+ * the partial. */
+#define WBX_CONT_CELLS 4           /* TP, FP, FN, TN */
+#define WBX_CONT_MAX_THRESHOLDS 16 /* per launch */
+int wbx_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int nthr,
+                            const void* p, const void* t, const double* thresholds /* DEVICE float64[nthr] */,
+                            const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -525,7 +552,8 @@ typedef enum wbx_fn {
   WBX_FN_DET_PARTIAL = 1, WBX_FN_ENS_PARTIAL = 2, WBX_FN_ENS2_PARTIAL = 3, WBX_FN_CAT_PARTIAL = 4, WBX_FN_CAT_EXCEED_FIELD = 5,
   WBX_FN_CONTRACT = 6, WBX_FN_CONTRACT_BITS = 7, WBX_FN_DET_BINNED = 8, WBX_FN_ENS_BINNED = 9, WBX_FN_ZONAL_SPECTRUM = 10,
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
-  WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19
+  WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
+  WBX_FN_CONTINGENCY_PARTIAL = 20
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

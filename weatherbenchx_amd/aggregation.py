@@ -319,6 +319,10 @@ class Aggregator:
     reduce_set = set(self.reduce_dims)
     if not reduce_set <= set(stat.dims):
       return None  # variables without every reduce dim are dropped (aggregation.py:305-309)
+    if isinstance(stat, lazy.LazyContingency) and stat.is_lazy:
+      fused = self._try_contingency(stat, reduce_set, use_mask, skipna)
+      if fused is not None:
+        return fused  # (else: `.data` is read below -- the host route)
     wp = self._cached_weight_product(stat)
     if wp is None:
       return None
@@ -382,6 +386,7 @@ class Aggregator:
     if not name.startswith('_w_'):
       self.__dict__.pop('_w_products', None)
       self.__dict__.pop('_w_dep_hints', None)
+      self.__dict__.pop('_w_cont_frames', None)
     object.__setattr__(self, name, value)
 
   def _cached_weight_product(self, stat: xr.DataArray):
@@ -517,6 +522,74 @@ class Aggregator:
       a = np.transpose(np.asarray(a, dtype=np.float64), order)
       a = stat.split_categories(a if pending else np.ascontiguousarray(a), cat_axis)
       return xr.DataArray(a, dims=final_dims, coords=coords, name=stat.name,
+                          attrs=stat.attrs, _raw_coords=True)
+    return AggregationState(mk(values), mk(counts))
+
+  def _try_contingency(self, stat: 'lazy.LazyContingency', reduce_set, use_mask, skipna):
+    """The fused route for a cell of a thresholded contingency table, or None for the host route.  Taken when the launch context
+    can make the call (engine.contingency_available: any other context object -- the NumPy plan interpreter has no library --
+    keeps the host route), the threshold dim is not reduced, and W does not involve it.  W is built on the statistic's frame
+    WITHOUT the threshold dim (plugins such as LatitudeBins broadcast their masks to whatever dims the statistic has): right for
+    this package's own weightings and binnings, which look at coordinates only; a plugin from elsewhere may look at the values,
+    and one that asks for the threshold coordinate does not find it -- both keep the host route."""
+    thr_dim = stat._threshold_dim  # pylint: disable=protected-access
+    if not lazy.FUSED_CONTINGENCY or thr_dim in reduce_set or not engine.contingency_available(_hip.default_context()):
+      return None
+    own = (binning.__name__, weighting.__name__)
+    if not all(type(m).__module__ in own for m in tuple(self.weigh_by or ()) + tuple(self.bin_by or ())):
+      return None
+    # (one W per frame OBJECT -- the four cells of a pair hand over the same one -- so that they meet in one cached launch even
+    #  where W is rebuilt on every call, as it is for plugins outside _cached_weight_product's list)
+    frame = stat.frame()
+    plugins = tuple(self.weigh_by or ()) + tuple(self.bin_by or ())
+    memo = self.__dict__.setdefault('_w_cont_frames', {})
+    mkey = (id(frame), len(self.weigh_by or ())) + tuple(id(m) for m in plugins)
+    hit = memo.get(mkey)
+    if hit is not None and hit[0]() is frame:
+      wp = hit[1]
+    else:
+      try:
+        wp = self._cached_weight_product(frame)
+      except KeyError:  # a coordinate the frame does not have (the threshold dim's): W is the full statistic's business
+        return None
+      if len(memo) > 16:
+        memo.clear()
+      memo[mkey] = (weakref.ref(frame), wp, plugins)
+    if wp is None:
+      return None
+    w_da, bin_dims = wp
+    if thr_dim in bin_dims or (w_da is not None and thr_dim in w_da.dims):
+      return None
+    return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
+
+  def _reduce_contingency(self, stat: 'lazy.LazyContingency', w_da, bin_dims, use_mask, skipna):
+    """One cell of a thresholded contingency table: the four cells of a (p, t) pair are the lane blocks of ONE launch
+    (wbx_contingency_partial), run by whichever cell comes first and kept on the group; this cell takes its block
+    values[cell * K:(cell + 1) * K] as a view, the thresholds come back as the statistic's trailing dimension."""
+    grp = stat._group  # pylint: disable=protected-access
+    thr_dim = stat._threshold_dim  # pylint: disable=protected-access
+    key = self._cache_key(w_da, bin_dims, use_mask, skipna, ('cont',))
+    hit = grp.cache.get(key)
+    if hit is None:
+      hit = grp.cache[key] = grp.reduce(self.reduce_dims, w_da, bin_dims, use_mask=use_mask, skipna=skipna)
+    values, counts, out_dims = hit
+    k, cell = stat.nthr, stat._cell  # pylint: disable=protected-access
+    values, counts = values[cell * k:(cell + 1) * k], counts[cell * k:(cell + 1) * k]
+    dims_in = (thr_dim,) + tuple(out_dims)
+    final_dims = tuple(d for d in tuple(grp.dims) + (thr_dim,) if d in dims_in) + tuple(bin_dims)
+    # (exactly the host route's coordinates: every one whose dims all survive stays, a `mask` among them -- see _aggregate)
+    coords = {n: x for n, x in stat._coords.items() if set(x[0]) <= set(final_dims)}  # pylint: disable=protected-access
+    if w_da is not None:
+      for n, x in w_da._coords.items():  # pylint: disable=protected-access
+        if set(x[0]) <= set(final_dims):
+          coords.setdefault(n, x)
+    order = [dims_in.index(d) for d in final_dims]
+    pending = engine.deferred_active() is not None
+
+    def mk(a):
+      a = np.transpose(np.asarray(a, dtype=np.float64), order)  # (a slice of lanes, transposed: still a view)
+      # deferred: keep the view of the buffer the GPU is still writing / accumulating -- no reads here
+      return xr.DataArray(a if pending else np.ascontiguousarray(a), dims=final_dims, coords=coords, name=stat.name,
                           attrs=stat.attrs, _raw_coords=True)
     return AggregationState(mk(values), mk(counts))
 

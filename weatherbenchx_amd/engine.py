@@ -340,9 +340,12 @@ def _planned_inner(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, f
   hit = _fast_plan_cache.get(sig)
   if hit is None:
     plan = planner.build_s1_plan(dims, sizes, layouts, reduce_dims, wdep_dims=wdep, gather=gather, flags=flags,
-                                 allow_vec4=(kind == 'det' and x_weights is None and force_x is None), force_x_dim=force_x,
+                                 allow_vec4=(kind in ('det', 'cont') and x_weights is None and force_x is None), force_x_dim=force_x,
                                  fold_x=False if x_weights is None else
                                  (True if kind == 'det' else ('point64' if one_wave else 'point')))
+    if kind == 'cont' and plan.plane_rows > 0:  # 16-byte loads yes, plane mode no: wbx_contingency_partial walks rows
+      plan = planner.build_s1_plan(dims, sizes, layouts, reduce_dims, wdep_dims=wdep, gather=gather, flags=flags,
+                                   allow_vec4=False, force_x_dim=force_x)
     if x_weights is not None and plan.plane_rows > 0:
       assert not plan.x_kept and plan.vec == 1 and plan.nx == x_weights.size
       plan.x_weights = np.ascontiguousarray(x_weights, dtype=np.float64)
@@ -417,6 +420,28 @@ def _scratch(ctx, slot: str, nbytes: int):
     buf = ctx.alloc(int(nbytes * 1.25) + 256)
     _scratch_bufs[key] = buf
   return buf
+
+
+def _threshold_table(ctx, thresholds):
+  """The device copy of a float64 threshold table, uploaded once per (device, contents)."""
+  tkey = (ctx.device_id, np.asarray(thresholds, np.float64).tobytes())
+  thr = _thr_cache.get(tkey)
+  if thr is None:
+    if len(_thr_cache) > 64:
+      _thr_cache.clear()
+    thr = _thr_cache[tkey] = ctx.upload(np.asarray(thresholds, np.float64))
+  return thr
+
+
+def contingency_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_contingency_partial: a real library context whose library exports the entry point.  Any
+  other context object (the NumPy plan interpreter of the CPU tests has no library) keeps the host route."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_contingency_partial', None) is not None
+  except AttributeError:
+    return False
 
 
 def new_context() -> _hip.Context:
@@ -713,6 +738,11 @@ def _run_s1(ctx, kind: str, dplan: _PlanOnDevice, plan: planner.S1Plan, devs: Se
       m, mstride, n_t, tstride = ens
       _hip.check(ctx.lib.wbx_ens2_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(m), int(mstride), int(n_t), int(tstride),
                                           ptr(devs[0]), ptr(devs[1]), ptr(devs[3]), C.c_void_p(out.ptr)), 'wbx_ens2_partial')
+    elif kind == 'cont':
+      nthr, thr = cat
+      _hip.check(ctx.lib.wbx_contingency_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(nthr), ptr(devs[0]),
+                                                 ptr(devs[1]), ptr(thr), ptr(devs[3]), C.c_void_p(out.ptr)),
+                 'wbx_contingency_partial')
     elif kind == 'cat':
       cfunc, ncat, m, mstride, thr, _ = cat
       _hip.check(ctx.lib.wbx_cat_partial(ctx.handle, C.byref(dplan.struct), int(cfunc), dtype_code, int(ncat), int(m),
@@ -1410,7 +1440,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   """Fused statistics + weighted/binned reduction.
 
   kind 'det' / 'ens' / 'cat' (indicator statistics: `cat` = {'func', 'ncat', 'thresholds' (float64 ndarray or None),
-  'member_dim' (or None), 'M'}; one value lane per category).
+  'member_dim' (or None), 'M'}; one value lane per category) / 'cont' (thresholded contingency tables,
+  wbx_contingency_partial: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
+  cell * nthr + k, cell in (TP, FP, FN, TN)).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1476,6 +1508,11 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   plan, dplan = hit if hit is not None else _planned(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, flags)
   nl = _hip.DET_LANES[func] if kind == 'det' else (int(cat['ncat']) if kind == 'cat' else
                                                    (_hip.ENS2_LANES if kind == 'ens2' else _hip.ENS_LANES))
+  if kind == 'cont':
+    nthr = int(np.asarray(cat['thresholds']).size)
+    if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
+      raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
+    nl = _hip.CONT_CELLS * nthr
   counted = bool(flags & 3)
   shared_count = counted and not (flags & _hip.FLAG_SKIPNA)  # mask only: one count lane for every statistic
   nl_total = nl + 1 if shared_count else nl * (2 if counted else 1)
@@ -1487,21 +1524,20 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   if kind == 'cat':
     thr = None
     if cat.get('thresholds') is not None and thr_field is None:
-      tkey = (ctx.device_id, np.asarray(cat['thresholds'], np.float64).tobytes())
-      thr = _thr_cache.get(tkey)
-      if thr is None:
-        if len(_thr_cache) > 64:
-          _thr_cache.clear()
-        thr = _thr_cache[tkey] = ctx.upload(np.asarray(cat['thresholds'], np.float64))
+      thr = _threshold_table(ctx, cat['thresholds'])
     cat_args = (cat['func'], nl, cat.get('M', 1) if member_dim else 1,
                 devs[0].layout.stride(member_dim) if member_dim else 0, thr,
                 None if thr_field is None else devs[2].layout.stride(cat['cat_dim']))
+  cont_thr = None
+  if kind == 'cont':
+    cont_thr = _threshold_table(ctx, cat['thresholds'])
+    cat_args = (nthr, cont_thr)
   w_buf = _device_w(ctx, plan, w_da, bin_dims)
   # (a chunk that is being recorded: the record keeps what the launches below point at -- plan tables, weights / bins / atom
   #  tables, inputs that do not follow the chunk such as the climatology, threshold tables)
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
-  replay.keep(dplan, w_buf, cat_args[4] if cat_args else None,
+  replay.keep(dplan, w_buf, cont_thr if kind == 'cont' else (cat_args[4] if cat_args else None),
               devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None)
   bin_shape = w_buf.bin_shape
   s2 = planner.build_s2_plan(plan, nl_total, w_buf.shape[-1])

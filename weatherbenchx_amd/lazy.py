@@ -40,6 +40,11 @@ def cat_lanes_per_launch(func: int, masked: bool, skipna: bool) -> int:
   return lanes // 2 if skipna else (lanes - 1 if masked else lanes)
 
 
+# False (WBX_FUSED_CONTINGENCY=0): thresholded contingency tables (categorical.TruePositives .. behind wrappers.ContinuousToBinary)
+# are materialised and reduced on the host route as before wbx_contingency_partial existed (A/B timing and tests).
+FUSED_CONTINGENCY = os.environ.get('WBX_FUSED_CONTINGENCY', '1') != '0'
+CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
+
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
 
 
@@ -200,7 +205,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont'):
       return [self.p, self.t], 0
     if self.clim is not None:
       return [self.p, self.t, self.clim.source], _hip.DET6
@@ -217,6 +222,8 @@ class FusedGroup:
                                       w_da, bin_dims, mask=mask, skipna=skipna, ens=self.ens)
     if self.kind == 'cat':
       return self._reduce_cat(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
+    if self.kind == 'cont':
+      return self._reduce_cont(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
     return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
                                bin_dims, func=func, mask=mask, skipna=skipna, clim=self.clim, ens=ens)
 
@@ -242,6 +249,27 @@ class FusedGroup:
         values.append(np.array(v, dtype=np.float64))  # (own memory: the next launch reuses the result buffers)
         counts.append(np.array(c, dtype=np.float64))
     return np.concatenate(values, axis=0), np.concatenate(counts, axis=0), out_dims
+
+  def _reduce_cont(self, inputs, reduce_dims, w_da, bin_dims, mask, skipna):
+    """Thresholded contingency tables: one launch for up to _hip.CONT_MAX_THRESHOLDS thresholds; more are cut into blocks --
+    thresholds are independent of one another --, one launch each, joined on the host cell by cell: the result is
+    (4 * K,) + out_dims with lane cell * K + k whatever the number of launches."""
+    thr = np.asarray(self.cat['thresholds'], np.float64)
+    nthr, block = int(thr.size), _hip.CONT_MAX_THRESHOLDS
+    if nthr <= block:
+      return engine.reduce_statistics('cont', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                      skipna=skipna, cat={'thresholds': thr})
+    values, counts, out_dims = [], [], None
+    with engine.synchronous_results():  # the blocks are joined on the host right away
+      for k0 in range(0, nthr, block):
+        sub = np.ascontiguousarray(thr[k0:k0 + block])
+        v, c, out_dims = engine.reduce_statistics('cont', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                                  skipna=skipna, cat={'thresholds': sub})
+        # (own memory: the next launch reuses the result buffers) -- (cell, k of the block) + out_dims
+        values.append(np.array(v, dtype=np.float64).reshape((_hip.CONT_CELLS, sub.size) + v.shape[1:]))
+        counts.append(np.array(c, dtype=np.float64).reshape((_hip.CONT_CELLS, sub.size) + c.shape[1:]))
+    join = lambda parts: np.concatenate(parts, axis=1).reshape((_hip.CONT_CELLS * nthr,) + parts[0].shape[2:])
+    return join(values), join(counts), out_dims
 
   def _cat_blocks(self, block: int):
     """self.cat cut into runs of at most `block` categories (kept: a block's threshold table / field is uploaded once)."""
@@ -580,6 +608,82 @@ class LazyCategorical(xr.LazyPickleMixin, xr.DataArray):
   @property
   def dtype(self):
     return np.dtype(np.float64)
+
+
+class LazyContingency(xr.LazyPickleMixin, xr.DataArray):
+  """One cell (TruePositives / FalsePositives / FalseNegatives / TrueNegatives) of the contingency table of (p > thr, t > thr)
+  along a new trailing `threshold_dim`: what `_Indicator` of the `ContinuousToBinary`-transformed inputs is.  The four cells of
+  one (p, t) pair and threshold list share a FusedGroup of kind 'cont', so the Aggregator gets all of them from one launch
+  (wbx_contingency_partial).  Reading `.data` materialises this cell on the host exactly as the unfused route does -- float32
+  indicator arithmetic on the binarised inputs -- and needs no device."""
+
+  def __init__(self, group: FusedGroup, cell: int, threshold_dim: str, name=None):
+    self._data = None
+    self._dims = tuple(group.dims) + (threshold_dim,)
+    self.name = name
+    self.attrs = {}
+    self._coords = dict(group.coords)
+    self._coords[threshold_dim] = ((threshold_dim,), np.asarray(group.cat['coord']))
+    self._group = group
+    self._cell = int(cell)
+    self._threshold_dim = threshold_dim
+
+  @property
+  def is_lazy(self) -> bool:
+    return self._data is None
+
+  @property
+  def nthr(self) -> int:
+    return int(np.asarray(self._group.cat['thresholds']).size)
+
+  def frame(self) -> xr.DataArray:
+    """The statistic's frame without the threshold dim -- dims, sizes, coordinates (the mask among them), a payload of zeros that
+    takes no memory: what coordinate-only weightings and binnings are asked for their W with (one object per group)."""
+    grp = self._group
+    if getattr(grp, 'frame_proxy', None) is None:
+      zeros = np.broadcast_to(np.zeros((), np.float32), tuple(grp.sizes[d] for d in grp.dims))
+      grp.frame_proxy = xr.DataArray._assemble(zeros, tuple(grp.dims), dict(grp.coords), name=self.name)  # pylint: disable=protected-access
+    return grp.frame_proxy
+
+  @property
+  def data(self):
+    if self._data is None:
+      from weatherbenchx_amd.metrics import categorical, wrappers  # pylint: disable=g-import-not-at-top
+      grp = self._group
+      values = list(grp.cat['values'])
+      pb = wrappers.binarize_thresholds(grp.p, values, self._threshold_dim)
+      tb = wrappers.binarize_thresholds(grp.t, values, self._threshold_dim)
+      predicted, observed = ((True, True), (True, False), (False, True), (False, False))[self._cell]
+      out = categorical._indicator(pb, tb, predicted, observed)  # pylint: disable=protected-access
+      self._data = out.transpose(*self._dims).data
+    return self._data
+
+  @property
+  def shape(self):
+    return tuple(self._group.sizes[d] for d in self._group.dims) + (self.nthr,)
+
+  @property
+  def dtype(self):
+    return np.dtype(np.float32)
+
+
+def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr.DataArray:
+  """Cell `cell` (0..3: TP, FP, FN, TN) of the 2x2 table of (p > thr_k, t > thr_k) as a LazyContingency.  `thresholds`: the
+  plain sequence of real numbers a ContinuousToBinary was built with; the (p, t) objects, the thresholds' bytes and the dim key
+  the group, so the four cells of a pair meet in one group."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if threshold_dim in p.dims or threshold_dim in t.dims:
+    raise ValueError(f'{threshold_dim!r} is already a dimension of the inputs')
+  values = list(thresholds)
+  thr = np.asarray(values, np.float64).reshape(-1)
+  table = p.__dict__.get('_wbx_groups')
+  ckey = ('cont', threshold_dim, thr.tobytes())
+  if not (table and any(k[0] == 'cont' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and k[4] == ckey
+                        and v[0]() is t and v[1]() is not None for k, v in table.items())):
+    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier cell has checked their frames)
+  cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim}
+  grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
+  return LazyContingency(grp, cell, threshold_dim, name=p.name)
 
 
 ENS2_LANE = {'CRPSSkill': 0, 'UnbiasedEnsembleMeanSquaredError': 1}

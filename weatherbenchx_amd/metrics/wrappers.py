@@ -75,6 +75,13 @@ class WrappedStatistic(base.Statistic):
     return f'{self.statistic.unique_name}_{self.transform.which}_{self.transform.unique_name_suffix}'
 
   def compute(self, predictions, targets):
+    # a statistic may know a fused form of itself behind this very transform (categorical._Indicator behind ContinuousToBinary:
+    # one kernel instead of the binarised arrays); None: no, transform and compute as usual
+    fused = getattr(self.statistic, 'compute_with_transform', None)
+    if fused is not None:
+      out = fused(self.transform, predictions, targets)
+      if out is not None:
+        return out
     if self.transform.which in ('predictions', 'both'):
       predictions = xarray_tree.map_structure(self.transform.transform_fn, _as_tree(predictions))
     if self.transform.which in ('targets', 'both'):
