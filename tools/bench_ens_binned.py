@@ -98,5 +98,4 @@ print(json.dumps({'layout': layout, 'bins': 0 if no_bins else 34, 'lib': os.path
                   'ms_per_chunk': round(ms_chunk, 4), 'launches_per_chunk': launches, 'ms_per_launch': {k: round(v, 4) for k, v in per_kind.items()},
                   'kernel_ms_per_chunk': round(kernel_ms, 4),
                   'frac_of_hbm_peak_per_launch': {k: round(nbytes / (v * 1e-3) / 8e12, 4) for k, v in per_kind.items()},
-                  'rows': os.environ.get('WBX_ENS_ATOMS_ROWS', 'default'), 'ens_binned': os.environ.get('WBX_ENS_BINNED', '1'),
                   'crps_global': float(np.asarray(out['crps.v'].values).reshape(-1)[0])}))

@@ -579,22 +579,15 @@ det_atoms_kernel(S1Args a, BinnedArgs g) {
   }
 }
 
-// WBX_BINNED_ATOMS=0 sends every patch to the slot kernel (A/B timing); WBX_ATOMS_NT=0/1 pins the non-temporal hint
-static int atoms_setting(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
-}
-
 template <typename T, int FUNC, int MM, int K, int PD>
 static int launch_binned_k(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const double* wt, const uint64_t* bits,
                          int64_t nA, int64_t nBk, int64_t nBr, int64_t nj, int nbin, double* out, int wmode, const void* prepared,
                          bool mask_on_w, bool accumulate) {
   constexpr int NL = FUNC == WBX_DET6 ? 6 : (FUNC == WBX_DET3 ? 3 : 1);
   constexpr int NA = NL + (MM == 1 ? 1 : (MM >= 2 ? NL : 0));
-  static const int use_atoms = atoms_setting("WBX_BINNED_ATOMS", 1);
-  static const int use_merged = atoms_setting("WBX_BINNED_MERGED_MASK", 1);  // A/B timing
-  // the atom kernel addresses a row as (uniform base) + (32-bit lane offset)
-  bool atoms = use_atoms != 0;
+  // the atom kernel takes every patch it can (the slot kernel alone: 0.85 ms against 0.39 ms per public-benchmark chunk);
+  // it addresses a row as (uniform base) + (32-bit lane offset)
+  bool atoms = true;
   for (int i = 0; i < WBX_MAX_INPUTS; ++i)
     if ((plan->nx - 1) * plan->xstride[i] >= ((int64_t)1 << 31) / (int64_t)sizeof(double) || plan->xstride[i] < 0) atoms = false;
   BinnedArgs g;
@@ -604,15 +597,13 @@ static int launch_binned_k(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, con
   if (atoms) {
     constexpr int RW = ATOMS_RAGGED_WPB;
     const int64_t agrid1 = patch_grid<1>(g), agridw = patch_grid<RW>(g);
-    static const int order_env = atoms_setting("WBX_PATCH_ORDER", -1);
-    static const int nt_env = atoms_setting("WBX_ATOMS_NT", -1);
     const bool ragged_lines = (plan->nx * (int64_t)sizeof(T)) % 128 != 0;
-    const bool nt = nt_env >= 0 ? nt_env != 0 : !ragged_lines;
+    const bool nt = !ragged_lines;
     BinnedArgs ga = g;
-    ga.order = order_env >= 0 ? order_env : (ragged_lines ? 1 : 0);
+    ga.order = ragged_lines ? 1 : 0;
     bool merged = false;
     if constexpr (MM == 1) {
-      if (mask_on_w && use_merged != 0 && nj == plan->nx && nj > 1) {  // the mask lives on the atom ids' own index space
+      if (mask_on_w && nj == plan->nx && nj > 1) {  // the mask lives on the atom ids' own index space
         if (int rc = merge_mask_into_atom_ids(ctx, a, ga)) return rc;
         merged = true;
       }
@@ -724,11 +715,10 @@ extern "C" int wbx_binned_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, int64_t n
   WBX_REQUIRE(bits != nullptr && atoms_out != nullptr, "NULL pointer");
   WBX_REQUIRE(nA >= 1 && nBk >= 1 && nBr >= 1 && plan->nx >= 1 && plan->ndepth >= 1, "empty geometry");
   WBX_HIP(hipSetDevice(ctx->device));
-  static const int use_atoms = atoms_setting("WBX_BINNED_ATOMS", 1);
   BinnedArgs g;
   patch_geometry(g, nA * nBk, nBk, nBr, (w_on_x & WBX_BINNED_W_ON_X) ? plan->nx : 1, plan->ndepth, plan->nx);
   atoms_carve(g, atoms_out);
-  if (int rc = atoms_launch(ctx, g, bits, plan->ndepth, plan->nx, use_atoms != 0)) return rc;
+  if (int rc = atoms_launch(ctx, g, bits, plan->ndepth, plan->nx, true)) return rc;
   // tables without a patch that overflows the atom list need no slot-kernel launch behind them: remembered by address (this
   // call runs once per (bins, geometry); a later call that fills the same address again replaces the entry)
   auto* clean = static_cast<std::set<const void*>*>(ctx->atoms_clean);
@@ -740,7 +730,7 @@ extern "C" int wbx_binned_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, int64_t n
   WBX_HIP(hipStreamSynchronize(ctx->stream));
   bool any = false;
   for (size_t i = 0; i < n; ++i) any = any || host[i] < 0;
-  if (!any && use_atoms != 0) {
+  if (!any) {
     if (clean->size() > 64) clean->clear();
     clean->insert(atoms_out);
   }

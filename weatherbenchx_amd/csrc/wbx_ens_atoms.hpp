@@ -51,7 +51,7 @@ constexpr int ENS_ATOMS_NOUT = 6;  // written per (cell, bin): the five ensemble
 constexpr int ENS_ATOMS_NOUT2 = 12;  // ... and, in twin mode, the same six again over ALL points (mask ignored)
 constexpr int ENS_ATOMS_ROWS2 = 2 * ATOM_MAX;  // table rows per patch: an atom and its twin (the masked-out points of the atom)
 
-constexpr int64_t ENS_ATOMS_ROWS = 16;  // rows (= 64-point tiles) per patch; WBX_ENS_ATOMS_ROWS in the environment overrides
+constexpr int64_t ENS_ATOMS_ROWS = 16;  // rows (= 64-point tiles) per patch, cut by the tapered split table of patch_taper
 
 // (global_ptr / const_ptr and the stand-in tables wbx_zero_i64 / wbx_one_f64: wbx_common.hpp)
 
@@ -591,17 +591,6 @@ struct EnsBinnedCall {
   double* out;           // [nA][nBk][ENS_ATOMS_NOUT (twin mode: NOUT2)][nbin]
 };
 
-// WBX_ENS_ATOMS_TAPER=0: uniform row splits (A/B timing); default: the tapered table of patch_taper
-inline bool ens_atoms_taper() {
-  static const bool on = !(getenv("WBX_ENS_ATOMS_TAPER") && atoi(getenv("WBX_ENS_ATOMS_TAPER")) == 0);
-  return on;
-}
-
-inline int64_t ens_atoms_rows() {
-  static const int64_t rows = getenv("WBX_ENS_ATOMS_ROWS") && atol(getenv("WBX_ENS_ATOMS_ROWS")) > 0 ? atol(getenv("WBX_ENS_ATOMS_ROWS")) : ENS_ATOMS_ROWS;
-  return rows;
-}
-
 // Counters of the in-kernel sums (EnsAtomsArgs): zero when allocated, and every launch leaves them zero.
 inline int ens_atoms_counters(wbx_ctx* ctx, size_t n, uint32_t** out) {
   if (ctx->patch_counters_size < n) {
@@ -627,7 +616,7 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
   const int64_t cells = c.nA * c.nBk;
   // (the scratch is sized for the geometry patch_setup is about to choose: same call as inside it)
   BinnedArgs probe;
-  patch_geometry(probe, cells, c.nBk, c.nBr, c.nj, plan->ndepth, plan->nx, ens_atoms_rows(), ens_atoms_taper());
+  patch_geometry(probe, cells, c.nBk, c.nBr, c.nj, plan->ndepth, plan->nx, ENS_ATOMS_ROWS);
   const int64_t npatch = (int64_t)probe.nrs * probe.nxt;
   const int ng1 = (int)((npatch + ENS_ATOMS_G1 - 1) / ENS_ATOMS_G1), ng2 = (ng1 + ENS_ATOMS_G2 - 1) / ENS_ATOMS_G2;
   const bool masked = (plan->flags & WBX_FLAG_MASKED) != 0, skipna = (plan->flags & WBX_FLAG_SKIPNA) != 0;
@@ -637,7 +626,7 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
   const size_t n_tab = (size_t)probe.nblocks * ENS_ATOMS_ROWS2 * ENS_ATOMS_NQ, n_p1 = (size_t)cells * ng1 * NP, n_p2 = (size_t)cells * ng2 * NP;
   // (nacc = 0: no per-patch bin tables -- the sums over patches happen inside the kernel)
   if (int rc = patch_setup(ctx, g, nullptr, c.bits, cells, c.nBk, c.nBr, c.nj, plan->ndepth, plan->nx, 0, c.nbin, true, c.prepared,
-                           true, ens_atoms_rows(), n_tab + n_p1 + n_p2, &extra, ens_atoms_taper()))
+                           true, ENS_ATOMS_ROWS, n_tab + n_p1 + n_p2, &extra))
     return rc;
   EnsAtomsArgs e;
   e.wx = (c.w_on_x & WBX_BINNED_WT_X_ONLY) ? c.wt : nullptr;
@@ -667,13 +656,11 @@ int launch_ens_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const Ens
     }
     e.masked = twin_out ? 2 : 1;
   }
-  static const int nt_env = getenv("WBX_ENS_ATOMS_NT") ? atoi(getenv("WBX_ENS_ATOMS_NT")) : -1;
-  static const int order_env = getenv("WBX_PATCH_ORDER") ? atoi(getenv("WBX_PATCH_ORDER")) : -1;
   // rows that are not whole 128-byte lines (721 latitudes): neighbouring x tiles share their boundary lines -- x tile fastest
   // block order and no non-temporal hint, so that the second request of a line finds it in L2 (see det_atoms_kernel)
   const bool ragged_lines = (plan->nx * plan->xstride[0] * 4) % 128 != 0 || plan->xstride[0] != 1;
-  const bool nt = nt_env >= 0 ? nt_env != 0 : !ragged_lines;
-  g.order = order_env >= 0 ? order_env : (ragged_lines ? 1 : 0);
+  const bool nt = !ragged_lines;
+  g.order = ragged_lines ? 1 : 0;
   const int64_t grid = nt ? patch_grid<1>(g) : patch_grid<ENS_ATOMS_RAGGED_WPB>(g);
   const int mode = skipna ? 2 : (e.id_cell_rows ? 1 : 0);
   const dim3 block(nt ? 64 : 64 * ENS_ATOMS_RAGGED_WPB);

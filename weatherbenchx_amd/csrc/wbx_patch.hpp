@@ -29,7 +29,7 @@ struct BinnedArgs {
   const uint8_t* aidm;               // the same with masked-out points set to 255 (det_atoms_kernel<.., MERGED>), or NULL
   unsigned long long* words;         // [nBk][patch][ATOM_MAX]
   int32_t* nwords;                   // [nBk][patch]: entries in the list, -1 = more than ATOM_MAX (slot kernel takes it)
-  int32_t atoms;                     // 0: every patch goes to the slot kernel (A/B timing: WBX_BINNED_ATOMS=0)
+  int32_t atoms;                     // 0: every patch goes to the slot kernel (strides the atom kernel cannot address; stage 2)
   int32_t order;                     // block order: 0 cell fastest, 1 x tile fastest (see patch_decode)
   // Tapered row splits (patch_taper; the ensemble atom kernel): split rs = Br rows [split_br[rs], split_br[rs + 1]) instead of
   // rs * rows_per_split ..: an XCD walks a contiguous eighth of the splits in order (patch_decode), and the last splits of each
@@ -211,7 +211,8 @@ static __global__ void __launch_bounds__(256) det_binned_finish(int64_t npatch, 
 
 // Patch geometry: rows = nBr * D reduced rows of nx points per cell, cut into nrs row splits x nxt tiles of 64 x.
 // rows_hint > 0: patches of about that many rows instead (the ensemble atom kernel, wbx_ens_atoms.hpp: a row of a patch is a
-// 64-point tile of ~2.4 us there, so its patches are short).
+// 64-point tile of ~2.4 us there, so its patches are short), cut by the tapered split table where it fits (355 -> 339 us per
+// public probabilistic chunk against uniform splits).
 // The tapered split table: the Br rows are dealt to eight segments (one per XCD, see BinnedArgs::split_br) with the SAME number
 // of splits each -- patches of `s0` Br rows for the first ~70 % of a segment, then half, then quarter size.  -> false when the
 // table would not fit (the caller keeps uniform splits).
@@ -247,7 +248,7 @@ inline bool patch_taper(BinnedArgs& g, int64_t nBr, int64_t s0) {
 }
 
 inline void patch_geometry(BinnedArgs& g, int64_t cells, int64_t nBk, int64_t nBr, int64_t nj, int64_t D, int64_t nx,
-                           int64_t rows_hint = 0, bool taper = false) {
+                           int64_t rows_hint = 0) {
   g.taper = 0;
   g.nBk = nBk;
   g.nBr = nBr;
@@ -260,8 +261,7 @@ inline void patch_geometry(BinnedArgs& g, int64_t cells, int64_t nBk, int64_t nB
   // every patch and every 64-row batch pays a setup; rows that are not whole 128-byte lines (721 points) keep the shorter
   // patches: their neighbouring x tiles share boundary lines, which only hit in L2 while the tiles walk the same rows at
   // about the same time -- 5 splits of 288 rows fetched 1.21 x the algorithmic bytes, 9 of 160 rows 1.11 x)
-  static const int64_t target_env = getenv("WBX_BINNED_TARGET_WAVES") ? atol(getenv("WBX_BINNED_TARGET_WAVES")) : 0;
-  const int64_t target = target_env > 0 ? target_env : (nx % 32 == 0 ? 8192 : 16384);
+  const int64_t target = nx % 32 == 0 ? 8192 : 16384;
   int64_t want = (target + cells * g.nxt - 1) / (cells * g.nxt);
   if (want > (rows + 63) / 64) want = (rows + 63) / 64;
   if (want < 1) want = 1;
@@ -269,7 +269,7 @@ inline void patch_geometry(BinnedArgs& g, int64_t cells, int64_t nBk, int64_t nB
   g.rows_per_split = (rows + want - 1) / want;
   g.rows_per_split = (g.rows_per_split + D - 1) / D * D;  // whole Br rows per split: a (bk, br, x) point has ONE patch
   g.nrs = (int)((rows + g.rows_per_split - 1) / g.rows_per_split);
-  if (taper && rows_hint > 0) patch_taper(g, nBr, g.rows_per_split / D);
+  if (rows_hint > 0) patch_taper(g, nBr, g.rows_per_split / D);
   g.ncell = cells;
   g.nblocks = cells * (int64_t)g.nrs * g.nxt;
   g.order = 0;
@@ -309,12 +309,12 @@ inline int atoms_launch(wbx_ctx* ctx, BinnedArgs& g, const uint64_t* bits, int64
 inline int patch_setup(wbx_ctx* ctx, BinnedArgs& g, const double* wt, const uint64_t* bits, int64_t cells, int64_t nBk,
                        int64_t nBr, int64_t nj, int64_t D, int64_t nx, int nacc, int nbin, bool atoms = false,
                        const void* prepared = nullptr, bool tmp_written_by_kernels = false, int64_t rows_hint = 0,
-                       size_t extra_doubles = 0, double** extra_out = nullptr, bool taper = false) {
+                       size_t extra_doubles = 0, double** extra_out = nullptr) {
   g.wt = wt;
   g.bits = reinterpret_cast<const unsigned long long*>(bits);
   g.nbin = nbin;
   g.aidm = nullptr;
-  patch_geometry(g, cells, nBk, nBr, nj, D, nx, rows_hint, taper);
+  patch_geometry(g, cells, nBk, nBr, nj, D, nx, rows_hint);
   const int64_t npatch = (int64_t)g.nrs * g.nxt;
   const size_t n_tmp = (size_t)cells * npatch * nacc * nbin, n_poison = (size_t)cells * npatch * nacc;
   const size_t need = (n_tmp + n_poison + extra_doubles) * sizeof(double) + (prepared ? 0 : atoms_carve(g, nullptr));

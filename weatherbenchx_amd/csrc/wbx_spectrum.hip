@@ -943,8 +943,9 @@ __global__ void __launch_bounds__(256) zspec_fused_kernel(const float* __restric
 // Diagnostic instantiations -- WBX_SPECTRUM_KNOCK: kernels whose RESULTS ARE WRONG by design (timing only);
 // WBX_SPECTRUM_PROF=<file>: the phase-stamped kernels, counters appended to a file -- exist only in a library built with
 // -DWBX_DIAGNOSTICS (`make diag`: libwbx_hip_diag.so, what tools/kbench_spectrum_raw.py and tools/spec_phase_profile.py load
-// through WBX_LIBRARY_PATH).  The shipped library ignores both variables and says so once: a stray environment variable in a
-// production job must not be able to corrupt spectra or write files.
+// through WBX_LIBRARY_PATH): every launch ladder that names one sits under the same #ifdef, so the shipped library does not
+// even hold their code.  It ignores both variables and says so once: a stray environment variable in a production job must
+// not be able to corrupt spectra or write files.
 #ifdef WBX_DIAGNOSTICS
 static int spectrum_knock() {
   static const int knock = [] {
@@ -969,19 +970,10 @@ static void spectrum_diag_ignored() {
   }();
   (void)said;
 }
-static int spectrum_knock() {
-  spectrum_diag_ignored();
-  return 0;
-}
-static const char* spectrum_prof_path() { return nullptr; }
 #endif
 
-// Launches zspec1440_kernel: as many one-wave teams per block as the LDS holds (12: tables + 12 x 11.4 KB), one block per
-// CU, and -- every team takes the same time -- a grid of exactly `rounds` resident sets.
-constexpr int SPECTRUM_SKEW_DEFAULT = 100;  // per mille of a team's rows (WBX_SPECTRUM_SKEW overrides; 0 / 40 / 70 / 100 / 130 / 200 / 250: 0.249 / 0.245 / 0.242 / 0.239 / 0.241 / 0.242 / 0.248 ms)
-
-static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t row_stride, int64_t nrows,
-                       const int32_t* group, const double* scale, double* power_out, int32_t ngroup, int32_t accumulate) {
+// The tables of the 1440-point kernels (zspec1440_tables) on the device: uploaded by the first launch that needs them.
+static int zspec1440_device_tables(wbx_ctx* ctx, FftState* st, const float2** out) {
   void*& tab = st->twiddles[-Z14_N];
   if (!tab) {
     std::vector<float2> host;
@@ -990,37 +982,62 @@ static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t r
     WBX_HIP(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
     WBX_HIP(hipStreamSynchronize(ctx->stream));
   }
-  static const int teams_env = getenv("WBX_SPECTRUM_1440_TEAMS") ? atoi(getenv("WBX_SPECTRUM_1440_TEAMS")) : 12;
-  const int nteam = teams_env < 1 ? 1 : (teams_env > 12 ? 12 : teams_env);
-  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)nteam * Z14_BUF * sizeof(v4);
-  // WBX_SPECTRUM_PROF=<file>: the phase-stamped instantiation; the eight counters are appended to the file per launch
-  const char* prof_path = spectrum_prof_path();
-  const void* fn = prof_path ? reinterpret_cast<const void*>(&zspec1440_kernel<true, 0>) : reinterpret_cast<const void*>(&zspec1440_kernel<false, 0>);
+  *out = reinterpret_cast<const float2*>(tab);
+  return 0;
+}
+
+// Resident blocks per CU of kernel `fn` at `threads` per block and `lds` bytes of dynamic LDS (LDS and VGPRs both limit it):
+// queried once per (kernel, LDS size).
+static int spec_blocks_per_cu(FftState* st, const void* fn, int threads, size_t lds, int* out) {
   int& per_cu = st->occupancy[std::make_pair(fn, lds)];
   if (per_cu == 0) {
     if (lds > 48 * 1024) WBX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * nteam, lds));
+    WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds));
     if (per_cu <= 0) per_cu = 1;
   }
-  int rounds = 1;
-  if (const char* e = getenv("WBX_SPECTRUM_ROUNDS")) rounds = atoi(e) > 0 ? atoi(e) : 1;
-  if (getenv("WBX_SPECTRUM_DEBUG")) fprintf(stderr, "zspec1440: teams/block=%d lds=%zu blocks/CU=%d\n", nteam, lds, per_cu);
-  int64_t teams = (int64_t)per_cu * ctx->num_cus * nteam * rounds;
+  *out = per_cu;
+  return 0;
+}
+
+// Launches zspec1440_kernel: as many one-wave teams per block as the LDS holds (12: tables + 12 x 11.4 KB), one block per
+// CU, and -- every team takes the same time -- a grid of exactly one resident set.
+constexpr int SPECTRUM_SKEW_DEFAULT = 100;  // per mille of a team's rows (0 / 40 / 70 / 100 / 130 / 200 / 250: 0.249 / 0.245 / 0.242 / 0.239 / 0.241 / 0.242 / 0.248 ms)
+
+static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t row_stride, int64_t nrows,
+                       const int32_t* group, const double* scale, double* power_out, int32_t ngroup, int32_t accumulate) {
+  const float2* tab = nullptr;
+  if (int rc = zspec1440_device_tables(ctx, st, &tab)) return rc;
+  constexpr int nteam = 12;
+  const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)nteam * Z14_BUF * sizeof(v4);
+#ifdef WBX_DIAGNOSTICS
+  // WBX_SPECTRUM_PROF=<file>: the phase-stamped instantiation; the eight counters are appended to the file per launch
+  const char* prof_path = spectrum_prof_path();
+  const void* fn = prof_path ? reinterpret_cast<const void*>(&zspec1440_kernel<true, 0>) : reinterpret_cast<const void*>(&zspec1440_kernel<false, 0>);
+#else
+  spectrum_diag_ignored();
+  const void* fn = reinterpret_cast<const void*>(&zspec1440_kernel<false, 0>);
+#endif
+  int per_cu = 0;
+  if (int rc = spec_blocks_per_cu(st, fn, 64 * nteam, lds, &per_cu)) return rc;
+  int64_t teams = (int64_t)per_cu * ctx->num_cus * nteam;
   if (teams > (nrows + 1) / 2) teams = (nrows + 1) / 2;
   int rows_per_team = (int)((nrows + teams - 1) / teams);
   rows_per_team += rows_per_team & 1;  // whole pairs
   teams = (nrows + rows_per_team - 1) / rows_per_team;
   const unsigned blocks = (unsigned)((teams + nteam - 1) / nteam);
   // rows the oldest four waves of a block take more / the youngest four less (whole pairs), see the kernel
-  static const int skew_permille = getenv("WBX_SPECTRUM_SKEW") ? atoi(getenv("WBX_SPECTRUM_SKEW")) : SPECTRUM_SKEW_DEFAULT;
   int skew = 0;
-  if (nteam == 12 && rows_per_team >= 16) skew = 2 * (int)(((int64_t)rows_per_team * skew_permille + 1000) / 2000);
+  if (rows_per_team >= 16) skew = 2 * (int)(((int64_t)rows_per_team * SPECTRUM_SKEW_DEFAULT + 1000) / 2000);
   if (skew >= rows_per_team) skew = 0;
   // the records of this launch (teams walk contiguous rows: one record per team + one per group change + one per straddling pair)
   int64_t changes = 0;
   if (int rc = spec_group_changes(ctx, group, nrows, &changes)) return rc;
   SpecRecs recs;
   if (int rc = spec_recs_prepare(ctx, st, (int64_t)blocks * nteam, 2 * changes, Z14_N2 + 1, &recs)) return rc;
+#define WBX_Z14_LAUNCH(...)                                                                                                          \
+  hipLaunchKernelGGL((zspec1440_kernel<__VA_ARGS__>), dim3(blocks), dim3(64 * nteam), lds, ctx->stream, field, row_stride, nrows, \
+                     rows_per_team, skew, tab, group, scale, recs, prof)
+#ifdef WBX_DIAGNOSTICS
   if (prof_path) {
     static unsigned long long* prof = nullptr;  // (diagnostic path: one device, never freed)
     unsigned long long host[26];
@@ -1031,8 +1048,7 @@ static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t r
       WBX_HIP(hipMemcpyAsync(prof, host, sizeof(host), hipMemcpyHostToDevice, ctx->stream));
       WBX_HIP(hipStreamSynchronize(ctx->stream));
     }
-    hipLaunchKernelGGL((zspec1440_kernel<true, 0>), dim3(blocks), dim3(64 * nteam), lds, ctx->stream, field, row_stride, nrows,
-                       rows_per_team, skew, reinterpret_cast<const float2*>(tab), group, scale, recs, prof);
+    WBX_Z14_LAUNCH(true, 0);
     WBX_HIP(hipGetLastError());
     if (int rc = spec_close(ctx, recs, ngroup, Z14_N2 + 1, 1, power_out, nullptr, accumulate)) return rc;
     if (timing_only) return 0;
@@ -1044,60 +1060,54 @@ static int launch_1440(wbx_ctx* ctx, FftState* st, const float* field, int64_t r
     }
     return 0;
   }
-  const int knock = spectrum_knock();  // diagnostic, wrong results
-#define WBX_Z14_LAUNCH(KN)                                                                                                 \
-  hipLaunchKernelGGL((zspec1440_kernel<false, KN>), dim3(blocks), dim3(64 * nteam), lds, ctx->stream, field, row_stride, nrows, \
-                     rows_per_team, skew, reinterpret_cast<const float2*>(tab), group, scale, recs,                        \
-                     static_cast<unsigned long long*>(nullptr))
-  switch (knock) {
-    case 1: WBX_Z14_LAUNCH(1); break;
-    case 2: WBX_Z14_LAUNCH(2); break;
-    case 6: WBX_Z14_LAUNCH(6); break;
-    case 7: WBX_Z14_LAUNCH(7); break;
-    case 8: WBX_Z14_LAUNCH(8); break;
-    case 14: WBX_Z14_LAUNCH(14); break;
-    case 15: WBX_Z14_LAUNCH(15); break;
-    case 17: hipLaunchKernelGGL((zspec1440_kernel<false, 0, true, true>), dim3(blocks), dim3(64 * nteam), lds, ctx->stream, field, row_stride, nrows, rows_per_team, skew, reinterpret_cast<const float2*>(tab), group, scale, recs, static_cast<unsigned long long*>(nullptr)); break;  // loads in front of pass 1
-    case 16: hipLaunchKernelGGL((zspec1440_kernel<false, 0, false>), dim3(blocks), dim3(64 * nteam), lds, ctx->stream, field, row_stride, nrows, rows_per_team, skew, reinterpret_cast<const float2*>(tab), group, scale, recs, static_cast<unsigned long long*>(nullptr)); break;  // no priority rotation
-    default: WBX_Z14_LAUNCH(0); break;
+#endif
+  unsigned long long* const prof = nullptr;
+#ifdef WBX_DIAGNOSTICS
+  switch (spectrum_knock()) {  // diagnostic, wrong results
+    case 1: WBX_Z14_LAUNCH(false, 1); break;
+    case 2: WBX_Z14_LAUNCH(false, 2); break;
+    case 6: WBX_Z14_LAUNCH(false, 6); break;
+    case 7: WBX_Z14_LAUNCH(false, 7); break;
+    case 8: WBX_Z14_LAUNCH(false, 8); break;
+    case 14: WBX_Z14_LAUNCH(false, 14); break;
+    case 15: WBX_Z14_LAUNCH(false, 15); break;
+    case 17: WBX_Z14_LAUNCH(false, 0, true, true); break;  // loads in front of pass 1
+    case 16: WBX_Z14_LAUNCH(false, 0, false); break;       // no priority rotation
+    default: WBX_Z14_LAUNCH(false, 0); break;
   }
+#else
+  WBX_Z14_LAUNCH(false, 0);
+#endif
 #undef WBX_Z14_LAUNCH
   WBX_HIP(hipGetLastError());
   return spec_close(ctx, recs, ngroup, Z14_N2 + 1, 1, power_out, nullptr, accumulate);
 }
 
 // Launches zspec1440_latfast_kernel over nslab slabs of rps adjacent rows (row_stride 1, longitude strided).
-constexpr int SPECTRUM_LF_PRIO_DEFAULT = 1;  // (0 / 1 / 2: 0.3673 / 0.3630 / 0.3674 ms back to back on one box) user priority of a block's waves by age (WBX_SPECTRUM_LF_PRIO overrides), see the kernel
+constexpr int SPECTRUM_LF_PRIO_DEFAULT = 1;  // (0 / 1 / 2: 0.3673 / 0.3630 / 0.3674 ms back to back on one box) user priority of a block's waves by age, see the kernel
 
 static int launch_1440_latfast(wbx_ctx* ctx, FftState* st, const float* field, int64_t lon_stride, const int64_t* d_slab_off,
                                int64_t rps, int64_t nslab, const int32_t* group, const double* scale, double* power_out,
                                int32_t ngroup, int32_t accumulate) {
-  void*& tab = st->twiddles[-Z14_N];
-  if (!tab) {
-    std::vector<float2> host;
-    zspec1440_tables(host);
-    WBX_HIP(hipMalloc(&tab, host.size() * sizeof(float2)));
-    WBX_HIP(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
-    WBX_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  const float2* tab = nullptr;
+  if (int rc = zspec1440_device_tables(ctx, st, &tab)) return rc;
   const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)Z14_TEAMS * Z14_BUFL * sizeof(v4) + (size_t)(Z14_N2 + 2) * sizeof(double);
+#ifdef WBX_DIAGNOSTICS
   const char* prof_path = spectrum_prof_path();
   const void* fn = prof_path ? reinterpret_cast<const void*>(&zspec1440_latfast_kernel<true, 0>) : reinterpret_cast<const void*>(&zspec1440_latfast_kernel<false, 0>);
-  int& per_cu = st->occupancy[std::make_pair(fn, lds)];
-  if (per_cu == 0) {
-    WBX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * Z14_TEAMS, lds));
-    if (per_cu <= 0) per_cu = 1;
-  }
+#else
+  spectrum_diag_ignored();
+  const void* fn = reinterpret_cast<const void*>(&zspec1440_latfast_kernel<false, 0>);
+#endif
+  int per_cu = 0;
+  if (int rc = spec_blocks_per_cu(st, fn, 64 * Z14_TEAMS, lds, &per_cu)) return rc;
   int nlocal = per_cu * ctx->num_cus / 8;  // blocks per XCD
   if (nlocal < 1) nlocal = 1;
   // runs per slab: 22 rows = 11 of the 12 teams.  Measured on configs[3] (721 rows per slab, 32 blocks per XCD), ms per
   // field for 31 / 32 / 33 / 34 / 36 / 40 / 48 runs: 0.396 / 0.418 / 0.389 / 0.425 / 0.393 / 0.421 / 0.512 -- 32 runs, where
   // the 32 blocks of an XCD walk the same longitudes of ONE slab in lockstep, is the slowest of the neighbours (FETCH 1.06 x
   // algorithmic against 1.09 x for 33: the shared lines are found in L2 either way)
-  int64_t runs = (rps + 21) / 22;
-  if (const char* e = getenv("WBX_SPECTRUM_LF_RUNS")) runs = atoi(e) >= (rps + Z14_RUN - 1) / Z14_RUN ? atoi(e) : runs;  // A/B timing
-  static const int lf_prio = getenv("WBX_SPECTRUM_LF_PRIO") ? atoi(getenv("WBX_SPECTRUM_LF_PRIO")) : SPECTRUM_LF_PRIO_DEFAULT;
+  const int64_t runs = (rps + 21) / 22;
   const int64_t per_xcd = ((nslab + 7) / 8) * runs;  // (slab, run) pairs of the busiest XCD
   if (per_xcd < nlocal) nlocal = (int)per_xcd;
   // the records of this launch: the block's table goes out when the step's group differs from the last one's (at most once per
@@ -1109,20 +1119,19 @@ static int launch_1440_latfast(wbx_ctx* ctx, FftState* st, const float* field, i
   const int64_t own = 13 * changes < 2 * rps * nslab ? 13 * changes : 2 * rps * nslab;
   SpecRecs recs;
   if (int rc = spec_recs_prepare(ctx, st, nslab * runs, own, Z14_N2 + 1, &recs)) return rc;  // static: one slot per step
+#define WBX_Z14LF_LAUNCH(...)                                                                                                        \
+  hipLaunchKernelGGL((zspec1440_latfast_kernel<__VA_ARGS__>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field,     \
+                     lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs),          \
+                     SPECTRUM_LF_PRIO_DEFAULT, tab, group, scale, recs, prof)
+#ifdef WBX_DIAGNOSTICS
   if (prof_path) {
     static unsigned long long* prof = nullptr;  // (diagnostic path, see launch_1440)
     unsigned long long host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (!prof) WBX_HIP(hipMalloc(reinterpret_cast<void**>(&prof), sizeof(host)));
     WBX_HIP(hipMemcpyAsync(prof, host, sizeof(host), hipMemcpyHostToDevice, ctx->stream));
     WBX_HIP(hipStreamSynchronize(ctx->stream));
-    if (spectrum_knock() == 3)
-      hipLaunchKernelGGL((zspec1440_latfast_kernel<true, 3>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field,
-                         lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs), lf_prio,
-                         reinterpret_cast<const float2*>(tab), group, scale, recs, prof);
-    else
-      hipLaunchKernelGGL((zspec1440_latfast_kernel<true, 0>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field,
-                         lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs), lf_prio,
-                         reinterpret_cast<const float2*>(tab), group, scale, recs, prof);
+    if (spectrum_knock() == 3) WBX_Z14LF_LAUNCH(true, 3);
+    else WBX_Z14LF_LAUNCH(true, 0);
     if (int rc = spec_close(ctx, recs, ngroup, Z14_N2 + 1, 1, power_out, nullptr, accumulate)) return rc;
     WBX_HIP(hipMemcpyAsync(host, prof, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
     WBX_HIP(hipStreamSynchronize(ctx->stream));
@@ -1134,18 +1143,20 @@ static int launch_1440_latfast(wbx_ctx* ctx, FftState* st, const float* field, i
     }
     return 0;
   }
-  const int knock = spectrum_knock();  // diagnostic, wrong results
-#define WBX_Z14LF_LAUNCH(KN)                                                                                               \
-  hipLaunchKernelGGL((zspec1440_latfast_kernel<false, KN>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field,  \
-                     lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs), lf_prio,           \
-                     reinterpret_cast<const float2*>(tab), group, scale, recs, static_cast<unsigned long long*>(nullptr))
-  if (knock == 1) WBX_Z14LF_LAUNCH(1);
-  else if (knock == 2) WBX_Z14LF_LAUNCH(2);
-  else if (knock == 3) WBX_Z14LF_LAUNCH(3);
-  else if (knock == 9) hipLaunchKernelGGL((zspec1440_latfast_kernel<false, 0, 1>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field, lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs), lf_prio, reinterpret_cast<const float2*>(tab), group, scale, recs, static_cast<unsigned long long*>(nullptr));  // a quarter of the loads in front of pass 1, none behind the unpack
-  else if (knock == 8) hipLaunchKernelGGL((zspec1440_latfast_kernel<false, 0, 0>), dim3(8 * nlocal), dim3(64 * Z14_TEAMS), lds, ctx->stream, field, lon_stride, d_slab_off, rps, nslab, (nslab + 7) / 8, (int)runs, (int)(rps / runs), (int)(rps % runs), lf_prio, reinterpret_cast<const float2*>(tab), group, scale, recs, static_cast<unsigned long long*>(nullptr));  // the next run's loads in one burst
-
-  else WBX_Z14LF_LAUNCH(0);
+#endif
+  unsigned long long* const prof = nullptr;
+#ifdef WBX_DIAGNOSTICS
+  switch (spectrum_knock()) {  // diagnostic, wrong results
+    case 1: WBX_Z14LF_LAUNCH(false, 1); break;
+    case 2: WBX_Z14LF_LAUNCH(false, 2); break;
+    case 3: WBX_Z14LF_LAUNCH(false, 3); break;
+    case 9: WBX_Z14LF_LAUNCH(false, 0, 1); break;  // a quarter of the loads in front of pass 1, none behind the unpack
+    case 8: WBX_Z14LF_LAUNCH(false, 0, 0); break;  // the next run's loads in one burst
+    default: WBX_Z14LF_LAUNCH(false, 0); break;
+  }
+#else
+  WBX_Z14LF_LAUNCH(false, 0);
+#endif
 #undef WBX_Z14LF_LAUNCH
   WBX_HIP(hipGetLastError());
   return spec_close(ctx, recs, ngroup, Z14_N2 + 1, 1, power_out, nullptr, accumulate);
@@ -1179,8 +1190,7 @@ static int launch_fused(wbx_ctx* ctx, FftState* st, const FusedSpec& fs, const f
                         int64_t nrows, const int32_t* group, const double* scale, double* power_out, int32_t ngroup,
                         int32_t accumulate) {
   const int nlon = fs.n, n2 = fs.n2;
-  static const bool use_1440 = getenv("WBX_SPECTRUM_1440") == nullptr || atoi(getenv("WBX_SPECTRUM_1440")) != 0;
-  if (nlon == Z14_N && use_1440 && !getenv("WBX_SPECTRUM_TEAM"))  // (WBX_SPECTRUM_TEAM pins the generic kernel's team size)
+  if (nlon == Z14_N && !getenv("WBX_SPECTRUM_TEAM"))  // (WBX_SPECTRUM_TEAM pins the generic kernel's team size)
     return launch_1440(ctx, st, field, row_stride, nrows, group, scale, power_out, ngroup, accumulate);
   int64_t changes = 0;
   if (int rc = spec_group_changes(ctx, group, nrows, &changes)) return rc;
@@ -1216,21 +1226,15 @@ static int launch_fused(wbx_ctx* ctx, FftState* st, const FusedSpec& fs, const f
   const int ntr = n2 / 2 + 1;
   const size_t lds = (size_t)(n2 + ntr + (ntr & 1) + 2 * nteam * n2) * sizeof(float2);  // tables + one row PAIR per team
   const int kpt = (n2 / 2 + 1 + G - 1) / G;
-  int rounds = 3;  // a few sets of blocks per resident slot: the last set's imbalance is a fraction of one set
-  if (const char* e = getenv("WBX_SPECTRUM_ROUNDS")) rounds = atoi(e) > 0 ? atoi(e) : 1;
+  constexpr int rounds = 3;  // a few sets of blocks per resident slot: the last set's imbalance is a fraction of one set
   // A team sweeps a contiguous run of rows (one group for most of it).  Blocks all take the same time, so the grid is a
   // whole number of resident sets (blocks per CU from the occupancy query: LDS and VGPRs both limit it): 2048 blocks on
   // 1280 resident slots ran as 1.6 rounds, the last one 60 % empty.
 #define WBX_LAUNCH_FUSED_R(KPT, GG, RR)                                                                                 \
   do {                                                                                                              \
     const void* fn = reinterpret_cast<const void*>(&zspec_fused_kernel<KPT, GG, RR>);                               \
-    int& per_cu = st->occupancy[std::make_pair(fn, lds)]; /* queried once per (kernel, LDS size) */                 \
-    if (per_cu == 0) {                                                                                              \
-      if (lds > 48 * 1024) WBX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-      WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, GG == 64 ? 256 : GG, lds));                 \
-      if (per_cu <= 0) per_cu = 1;                                                                                  \
-    }                                                                                                               \
-    if (getenv("WBX_SPECTRUM_DEBUG")) fprintf(stderr, "zspec: G=%d lds=%zu blocks/CU=%d\n", GG, lds, per_cu);             \
+    int per_cu = 0;                                                                                                 \
+    if (int rc = spec_blocks_per_cu(st, fn, GG == 64 ? 256 : GG, lds, &per_cu)) return rc;                          \
     int64_t teams = (int64_t)per_cu * ctx->num_cus * nteam * rounds;                                                \
     if (teams > (nrows + 1) / 2) teams = (nrows + 1) / 2;                                                           \
     int rows_per_team = (int)((nrows + teams - 1) / teams);                                                         \
@@ -1244,13 +1248,11 @@ static int launch_fused(wbx_ctx* ctx, FftState* st, const FusedSpec& fs, const f
 #define WBX_LAUNCH_FUSED(KPT, GG) WBX_LAUNCH_FUSED_R(KPT, GG, 0)
 #define WBX_LAUNCH_FUSED_256(KPT)                                  \
   do {                                                             \
-    if (!prefetch) WBX_LAUNCH_FUSED_R(KPT, 256, 0);                \
-    else if (fs.radix[0] == 4) WBX_LAUNCH_FUSED_R(KPT, 256, 4);    \
+    if (fs.radix[0] == 4) WBX_LAUNCH_FUSED_R(KPT, 256, 4);         \
     else if (fs.radix[0] == 2) WBX_LAUNCH_FUSED_R(KPT, 256, 2);    \
     else if (fs.radix[0] == 5) WBX_LAUNCH_FUSED_R(KPT, 256, 5);    \
     else WBX_LAUNCH_FUSED_R(KPT, 256, 3);                          \
   } while (0)
-  static const bool prefetch = getenv("WBX_SPECTRUM_PREFETCH") == nullptr || atoi(getenv("WBX_SPECTRUM_PREFETCH")) != 0;
   if (G == 256) {
     if (kpt <= 2) WBX_LAUNCH_FUSED_256(2); else WBX_LAUNCH_FUSED_256(3);
   } else if (G == 128) {
@@ -1361,14 +1363,8 @@ static int launch_1440_det(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, 
                            const void* c, const int32_t* group, const double* scale, double* partial_out, double* power_p,
                            double* power_t, int32_t ngroup, const double* det_scale = nullptr, double* det_out = nullptr) {
   const bool fold = det_scale != nullptr;
-  void*& tab = st->twiddles[-Z14_N];
-  if (!tab) {
-    std::vector<float2> host;
-    zspec1440_tables(host);
-    WBX_HIP(hipMalloc(&tab, host.size() * sizeof(float2)));
-    WBX_HIP(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
-    WBX_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  const float2* tab = nullptr;
+  if (int rc = zspec1440_device_tables(ctx, st, &tab)) return rc;
   S1Args a;
   fill_args(plan, a);
   a.in[0] = p;
@@ -1378,12 +1374,8 @@ static int launch_1440_det(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, 
   const size_t lds = (size_t)Z14_TABLES * sizeof(float2) + (size_t)ZD_TEAMS * Z14_BUF * sizeof(v4);
   const void* fn = fold ? (has_c ? reinterpret_cast<const void*>(&zspec1440_det_kernel<true, true>) : reinterpret_cast<const void*>(&zspec1440_det_kernel<false, true>))
                         : (has_c ? reinterpret_cast<const void*>(&zspec1440_det_kernel<true>) : reinterpret_cast<const void*>(&zspec1440_det_kernel<false>));
-  int& per_cu = st->occupancy[std::make_pair(fn, lds)];
-  if (per_cu == 0) {
-    if (lds > 48 * 1024) WBX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * ZD_TEAMS, lds));
-    if (per_cu <= 0) per_cu = 1;
-  }
+  int per_cu = 0;
+  if (int rc = spec_blocks_per_cu(st, fn, 64 * ZD_TEAMS, lds, &per_cu)) return rc;
   const int64_t nrows = plan->nkey;
   int64_t teams = (int64_t)per_cu * ctx->num_cus * ZD_TEAMS;  // one resident set: every team takes the same time
   int64_t rows_per_team = (nrows + teams - 1) / teams;
@@ -1398,16 +1390,16 @@ static int launch_1440_det(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, 
   if (int rc = spec_recs_prepare(ctx, st, blocks * ZD_TEAMS, changes, 2 * (Z14_N2 + 1) + (fold ? ZD_TAIL : 0), &recs)) return rc;
   if (fold && has_c)
     hipLaunchKernelGGL((zspec1440_det_kernel<true, true>), dim3((unsigned)blocks), dim3(64 * ZD_TEAMS), lds, ctx->stream, a, nrows,
-                       (int)rows_per_team, reinterpret_cast<const float2*>(tab), group, scale, recs, det_scale);
+                       (int)rows_per_team, tab, group, scale, recs, det_scale);
   else if (fold)
     hipLaunchKernelGGL((zspec1440_det_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * ZD_TEAMS), lds, ctx->stream, a, nrows,
-                       (int)rows_per_team, reinterpret_cast<const float2*>(tab), group, scale, recs, det_scale);
+                       (int)rows_per_team, tab, group, scale, recs, det_scale);
   else if (has_c)
     hipLaunchKernelGGL((zspec1440_det_kernel<true>), dim3((unsigned)blocks), dim3(64 * ZD_TEAMS), lds, ctx->stream, a, nrows,
-                       (int)rows_per_team, reinterpret_cast<const float2*>(tab), group, scale, recs, (const double*)nullptr);
+                       (int)rows_per_team, tab, group, scale, recs, (const double*)nullptr);
   else
     hipLaunchKernelGGL((zspec1440_det_kernel<false>), dim3((unsigned)blocks), dim3(64 * ZD_TEAMS), lds, ctx->stream, a, nrows,
-                       (int)rows_per_team, reinterpret_cast<const float2*>(tab), group, scale, recs, (const double*)nullptr);
+                       (int)rows_per_team, tab, group, scale, recs, (const double*)nullptr);
   WBX_HIP(hipGetLastError());
   if (fold) return spec_close(ctx, recs, ngroup, Z14_N2 + 1, 2, power_p, power_t, 0, det_out, ZD_TAIL, has_c ? 6 : 3);
   return spec_close(ctx, recs, ngroup, Z14_N2 + 1, 2, power_p, power_t, 0);
@@ -1417,14 +1409,8 @@ static int launch_1440_det(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, 
 static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan* plan, bool has_c, const void* p, const void* t,
                                    const void* c, int64_t rps, const int32_t* group, const double* scale, double* partial_out,
                                    double* power_p, double* power_t, int32_t ngroup) {
-  void*& tab = st->twiddles[-Z14_N];
-  if (!tab) {
-    std::vector<float2> host;
-    zspec1440_tables(host);
-    WBX_HIP(hipMalloc(&tab, host.size() * sizeof(float2)));
-    WBX_HIP(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
-    WBX_HIP(hipStreamSynchronize(ctx->stream));
-  }
+  const float2* tab = nullptr;
+  if (int rc = zspec1440_device_tables(ctx, st, &tab)) return rc;
   S1Args a;
   fill_args(plan, a);
   a.in[0] = p;
@@ -1435,12 +1421,8 @@ static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan
                      (size_t)2 * (Z14_N2 + 2) * sizeof(double) + (size_t)ZL_GROUPS * 4 * 2 * 6 * sizeof(double);
   const void* fn = has_c ? reinterpret_cast<const void*>(&zspec1440_det_latfast_kernel<true>)
                          : reinterpret_cast<const void*>(&zspec1440_det_latfast_kernel<false>);
-  int& per_cu = st->occupancy[std::make_pair(fn, lds)];
-  if (per_cu == 0) {
-    WBX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    WBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ZL_THREADS, lds));
-    if (per_cu <= 0) per_cu = 1;
-  }
+  int per_cu = 0;
+  if (int rc = spec_blocks_per_cu(st, fn, ZL_THREADS, lds, &per_cu)) return rc;  // (~120 KB of LDS: always above the 48 KB default)
   const int64_t nslab = plan->nkey / rps;
   int nlocal = per_cu * ctx->num_cus / 8;  // blocks per XCD
   if (nlocal < 1) nlocal = 1;
@@ -1448,10 +1430,8 @@ static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan
   // 128-byte line (1440 = 32 x 45), so a run's 32-byte segment never straddles two lines.  The L1 keeps ~64 line requests in
   // flight whatever part of a line is used (pmc: TCP_PENDING_STALL 58 % of the cycles, 5.2 x the algorithmic bytes requested
   // from L2 with runs of 7-8 rows at arbitrary offsets): every line a CU asks for twice is bandwidth lost.
-  // WBX_SPECTRUM_ZL_EVEN=1: runs of equal length instead (A/B timing)
-  int64_t runs = (rps + ZL_TEAMS - 1) / ZL_TEAMS;
-  static const bool even_runs = getenv("WBX_SPECTRUM_ZL_EVEN") && atoi(getenv("WBX_SPECTRUM_ZL_EVEN"));
-  const int run_base = even_runs ? (int)(rps / runs) : ZL_TEAMS, run_rem = even_runs ? (int)(rps % runs) : 0;
+  const int64_t runs = (rps + ZL_TEAMS - 1) / ZL_TEAMS;
+  const int run_base = ZL_TEAMS, run_rem = 0;
   const int64_t per_xcd = ((nslab + 7) / 8) * runs;  // (slab, run) pairs of the busiest XCD
   if (per_xcd < nlocal) nlocal = (int)per_xcd;
   WBX_REQUIRE(runs < (int64_t)1 << 30, "launch too large");
@@ -1467,7 +1447,7 @@ static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan
   static const int knock = getenv("WBX_ZL_KNOCK") ? atoi(getenv("WBX_ZL_KNOCK")) : 0;  // diagnostic, wrong results
 #define WBX_ZL_LAUNCH(KN)                                                                                                      \
   hipLaunchKernelGGL((zspec1440_det_latfast_kernel<true, KN>), dim3(8 * nlocal), dim3(ZL_THREADS), lds, ctx->stream, a, rps, nslab, \
-                     (nslab + 7) / 8, (int)runs, run_base, run_rem, reinterpret_cast<const float2*>(tab), group, \
+                     (nslab + 7) / 8, (int)runs, run_base, run_rem, tab, group, \
                      scale, recs)
   if (has_c && knock) {
     switch (knock) {
@@ -1485,11 +1465,11 @@ static int launch_1440_det_latfast(wbx_ctx* ctx, FftState* st, const wbx_s1_plan
 #endif
   if (has_c)
     hipLaunchKernelGGL((zspec1440_det_latfast_kernel<true>), dim3(8 * nlocal), dim3(ZL_THREADS), lds, ctx->stream, a, rps, nslab,
-                       (nslab + 7) / 8, (int)runs, run_base, run_rem, reinterpret_cast<const float2*>(tab), group,
+                       (nslab + 7) / 8, (int)runs, run_base, run_rem, tab, group,
                        scale, recs);
   else
     hipLaunchKernelGGL((zspec1440_det_latfast_kernel<false>), dim3(8 * nlocal), dim3(ZL_THREADS), lds, ctx->stream, a, rps, nslab,
-                       (nslab + 7) / 8, (int)runs, run_base, run_rem, reinterpret_cast<const float2*>(tab), group,
+                       (nslab + 7) / 8, (int)runs, run_base, run_rem, tab, group,
                        scale, recs);
   WBX_HIP(hipGetLastError());
   return spec_close(ctx, recs, ngroup, Z14_N2 + 1, 2, power_p, power_t, 0);
@@ -1630,9 +1610,8 @@ static int zonal_spectrum_impl(wbx_ctx* ctx, const float* field, int64_t lon_str
     // 721 rows: 27.6 ms -> see DESIGN.md)
     // (Scratch tiles small enough to stay in the 256 MB Infinity Cache between the transpose and the FFT were measured
     // SLOWER: 16 / 32 / 64 / 128 / 256 MB -> 8.1 / 6.1 / 4.1 / 3.3 / 3.0 ms per configs[3] step; the short launches do
-    // not fill the chip.)  WBX_SPECTRUM_TILE_MB: A/B timing.
-    static const int tile_mb = getenv("WBX_SPECTRUM_TILE_MB") ? atoi(getenv("WBX_SPECTRUM_TILE_MB")) : 256;
-    int64_t tile = ((int64_t)(tile_mb > 0 ? tile_mb : 256) << 20) / ((int64_t)nlon * 4);
+    // not fill the chip.)
+    int64_t tile = ((int64_t)256 << 20) / ((int64_t)nlon * 4);
     tile -= tile & 1;
     if (tile < 2) tile = 2;
     if (tile > nrows) tile = nrows;
@@ -1656,9 +1635,7 @@ static int zonal_spectrum_impl(wbx_ctx* ctx, const float* field, int64_t lon_str
       }
       d_off = reinterpret_cast<int64_t*>(it->second);
     }
-    static const bool use_latfast = (getenv("WBX_SPECTRUM_1440") == nullptr || atoi(getenv("WBX_SPECTRUM_1440")) != 0) &&
-                                    (getenv("WBX_SPECTRUM_LATFAST") == nullptr || atoi(getenv("WBX_SPECTRUM_LATFAST")) != 0);
-    if (nlon == Z14_N && use_latfast && !getenv("WBX_SPECTRUM_TEAM"))
+    if (nlon == Z14_N && !getenv("WBX_SPECTRUM_TEAM"))
       return launch_1440_latfast(ctx, st, field, lon_stride, d_off, rps, nslab, group, scale, power_out, ngroup, accumulate);
     const size_t need = (size_t)tile * nlon * sizeof(float);
     if (st->scratch_size < need) {

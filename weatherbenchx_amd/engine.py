@@ -472,8 +472,8 @@ ALTERNATE_STREAMS = os.environ.get('WBX_ALTERNATE_STREAMS', '1') != '0'
 # starts in the tail of chunk k's.  Public probabilistic chunk with chunk records on and two chunks in flight
 # (tools/bench_replay.py, profiles/r05_replay.txt): 0.312 against 0.322 ms per chunk on one stream (mask coordinate 0.330 /
 # 0.340, NaN mask 0.334 / 0.349; kernel alone 0.312 / 0.327 / 0.333).  (With ONE chunk in flight the pair ran dry for ~50 us
-# while the host caught up and the same switch lost 5 %.)  0: every launch of a label on one stream (A/B timing).
-ALTERNATE_CHUNKS = os.environ.get('WBX_ALTERNATE_CHUNKS', '1') != '0'
+# while the host caught up and the same switch lost 5 %.)  False: every launch of a label on one stream (tools/bench_replay.py).
+ALTERNATE_CHUNKS = True
 ENS_PIPE = os.environ.get('WBX_ENS_PIPE', '1') != '0'  # the library reads the same variable (csrc/wbx_ens_impl.hpp)
 _stream_ring: list = []
 
@@ -522,7 +522,7 @@ def clear_caches():
 # where spectra._run_spectrum finds them instead of launching.  Nothing is registered -> nothing changes.
 _fusion_requests: dict = {}   # id(predictions DataArray) -> {'p', 't', 'entry', 'ngroup'}
 _fusion_parks: list = []      # arrays that carry a fused spectrum nobody has asked for yet
-FUSE_DET_SPECTRA = os.environ.get('WBX_FUSE_DET_SPECTRA', '1') != '0'
+FUSE_DET_SPECTRA = True  # False: spectra and deterministic lanes as separate launches (tests)
 # The same fusion on latitude-fastest fields (wbx_det_spectrum_slabs, csrc/wbx_zspec_det_latfast.hpp) is correct but NOT faster
 # than the three launches it replaces (configs[3] chunk on MI355X: 1.70 ms against 1.55 ms -- runs of eight adjacent rows use a
 # quarter of every 128-byte line a CU asks its L2 for, and the L1 keeps only so many line requests in flight):
@@ -621,8 +621,8 @@ class _FoldedS2:
 # Stage 2 of the deterministic lanes inside the fused det + spectra sweep where W is one weight per row of the plan
 # (GridAreaWeighting over (init_time, latitude, longitude)) and the spectra's groups are the outputs stage 2 would form: the
 # rows' sums are weighted and added up with the spectra's records instead of being stored row by row and contracted afterwards
-# (-8 % of the sweep, no 25 MB partial, no contraction launch; tools/kbench_det_spectrum.py).  0: wbx_det_spectrum + wbx_contract.
-FOLD_DET_SPECTRA = os.environ.get('WBX_FOLD_DET_SPECTRA', '1') != '0'
+# (-8 % of the sweep, no 25 MB partial, no contraction launch; tools/kbench_det_spectrum.py).  False: wbx_det_spectrum + wbx_contract (tests).
+FOLD_DET_SPECTRA = True
 
 
 def _try_det_spectra(ctx, inputs, dplan, plan, devs, dtype_code, func, make_out, fold=None):
@@ -892,9 +892,6 @@ def synchronous_results():
 # Under deferred_results() (and no accumulation) a reduction whose LAST kernel writes every element of its result exactly
 # once writes it straight into page-locked host memory: the separate device-to-host copy -- a blit kernel behind ~12 us
 # of dependency latency, 5 % of a public-benchmark chunk -- disappears.
-DIRECT_RESULTS = os.environ.get('WBX_DIRECT_RESULTS', '1') != '0'
-
-
 class _HostResult:
   """A result that its kernel has been told to write into page-locked host memory (`view`, valid after the state's fence)."""
 
@@ -909,8 +906,8 @@ class _AccumulatedInPlace:
     self.ptr = ptr
 
 
-# WBX_FUSED_ACC_ADD=0: every chunk result goes through a scratch buffer + wbx_acc_add (A/B; the round-4 path)
-FUSED_ACC_ADD = os.environ.get('WBX_FUSED_ACC_ADD', '1') != '0'
+# False: every chunk result goes through a scratch buffer + wbx_acc_add (the round-4 path; tests)
+FUSED_ACC_ADD = True
 
 
 def _result_target(ctx, shape, scratch_name, can_accumulate=False):
@@ -924,7 +921,7 @@ def _result_target(ctx, shape, scratch_name, can_accumulate=False):
       if ptr is not None:
         return ptr, _AccumulatedInPlace(ptr), True
     return _result_target(ctx, shape, scratch_name) + (False,)
-  if DIRECT_RESULTS and _deferred is not None and _accum is None and n:
+  if _deferred is not None and _accum is None and n:
     view = ctx.pinned_result(shape)
     return view.ctypes.data, _HostResult(view)
   out = _scratch(ctx, scratch_name, n * 8)
@@ -1234,7 +1231,6 @@ def _run_s2(ctx, s2: planner.S2Plan, partial_ptr: int, w_buf):
 # plus ~0.52 ms per GB of partials (written by stage 1, read back by the stage-2 patch kernel) -> break-even where
 # the partials are ~45 % of the inputs (about 10 inits per chunk for the 6-lane family).
 BINNED_MODE = 'auto'
-PREPARED_ATOMS = True  # False: wbx_det_binned recomputes the atom tables in every call (A/B timing and tests)
 FOLD_X_WEIGHTS = True  # False: keep x for stage 2 (plane mode / x-kept kernels), for A/B timing and tests
 BINNED_PARTIAL_RATIO = 0.45
 
@@ -1272,8 +1268,8 @@ def _run_binned(ctx, dplan: _PlanOnDevice, plan: planner.S1Plan, devs, dtype_cod
   # the atom tables (a patch's distinct membership words + every point's index) depend on the bins and the launch
   # geometry only: computed once per (W, geometry) and kept with the device copy of W
   akey = (id(ctx), nA, nBk, nBr, plan.ndepth, plan.nx, w_flags & _hip.BINNED_W_ON_X)
-  atoms = w_buf.atoms.get(akey) if PREPARED_ATOMS else None
-  if atoms is None and PREPARED_ATOMS:
+  atoms = w_buf.atoms.get(akey)
+  if atoms is None:
     nbytes = C.c_int64(0)
     _hip.check(ctx.lib.wbx_binned_atoms_size(C.byref(dplan.struct), nA, nBk, nBr, w_flags & _hip.BINNED_W_ON_X,
                                              C.byref(nbytes)), 'wbx_binned_atoms_size')
@@ -1287,7 +1283,7 @@ def _run_binned(ctx, dplan: _PlanOnDevice, plan: planner.S1Plan, devs, dtype_cod
     _hip.check(ctx.lib.wbx_det_binned(ctx.handle, C.byref(dplan.struct), func, dtype_code, ptr(devs[0]), ptr(devs[1]),
                                       ptr(devs[2]), ptr(devs[3]), C.c_void_p(wt_buf.ptr),
                                       C.c_void_p(w_buf.bufs[1].ptr), nA, nBk, nBr, w_flags | (_hip.BINNED_ACCUMULATE if add else 0), nbin,
-                                      C.c_void_p(atoms.ptr) if atoms is not None else None,
+                                      C.c_void_p(atoms.ptr),
                                       C.c_void_p(out_ptr)), 'wbx_det_binned')
   timed_launch(ctx, call, kind='det_binned', nbin=nbin, w_flags=w_flags)
   return handle, shape
@@ -1296,14 +1292,14 @@ def _run_binned(ctx, dplan: _PlanOnDevice, plan: planner.S1Plan, devs, dtype_cod
 # The ensemble family with weights, bins and mask in ONE pass (wbx_ens_binned, csrc/wbx_ens_atoms.hpp) whenever it applies:
 # rank form, float32, 2..64 members, boolean bin masks, separable weights; (r5) any validity mask -- also the per-point one
 # add_nan_mask_to_data builds, with strides along time / level -- and Aggregator(skipna=True).  False: the two-stage route
-# (x-kept ensemble kernel + wbx_contract_bits), for A/B timing and tests.
-ENS_BINNED = os.environ.get('WBX_ENS_BINNED', '1') != '0'
+# (x-kept ensemble kernel + wbx_contract_bits), for tests.
+ENS_BINNED = True
 ENS_BINNED_LANES = 6  # the five ensemble lanes + the count lane, always
 # With a mask, ONE launch yields the masked sums (lanes 0-5) and the sums over all points (lanes 6-11): the reference masks the
 # skill / unbiased-MSE / mean-MSE statistics of such a variable but not its spread / variance (statistics of the predictions
 # alone), which would otherwise be a second pass over the members.  The unmasked half is left with the predictions array
 # ('_wbx_twin') for the member-only group of the same predictions to pick up.  False: one launch per mask setting (A/B, tests).
-ENS_TWIN_MASK = os.environ.get('WBX_ENS_TWIN_MASK', '1') != '0'
+ENS_TWIN_MASK = True
 
 
 def _mask_on_w_only(plan: planner.S1Plan, mask_dev) -> bool:

@@ -508,7 +508,7 @@ def _same_mask(p: xr.DataArray, t: xr.DataArray) -> bool:
 
 # True: CRPSSpread(use_sort=False) launches the register-tiled O(M^2) pair kernel (EnsOpF32<..., PAIRWISE>) instead of the
 # rank-form kernel.  A measurement switch (bench.py's `pairwise_form`, tools/kbench.py): the results agree to ~1e-7.
-PAIR_FORM_KERNEL = os.environ.get('WBX_ENS_PAIR_FORM', '0') == '1'
+PAIR_FORM_KERNEL = False
 
 
 def ens_statistic(stat_name: str, p, t, ensemble_dim: str, *, use_sort=False, fair=True,
@@ -537,7 +537,7 @@ def ens_statistic(stat_name: str, p, t, ensemble_dim: str, *, use_sort=False, fa
   # reference's own CRPSSpread.unique_name leaves use_sort out (probabilistic.py:189-192), i.e. it treats the two forms as
   # one statistic.  On this hardware the rank form is the cheaper way to that number (51 members: 0.31 against 0.51 ms per
   # 1.73 GB) and all five lanes of a (p, t) pair come out of ONE launch, so both settings run the rank-form kernel; the
-  # register-tiled pair kernel stays reachable through PAIR_FORM_KERNEL (or WBX_ENS_PAIR_FORM=1) for measurements.
+  # register-tiled pair kernel stays reachable through PAIR_FORM_KERNEL for measurements.
   # skipna_ensemble needs per-point member counts: the generic pair-form kernel (WBX_FLAG_SKIPNA_ENS).
   pair = bool(skipna_ensemble) or (not use_sort and PAIR_FORM_KERNEL)
   params = {'algo': _hip.ENS_PAIRWISE if pair else _hip.ENS_SORT, 'fair': bool(fair), 'skipna': bool(skipna_ensemble)}

@@ -15,7 +15,6 @@ weatherbenchX/aggregation.py:297-335, for arbitrary loader dim orders
 from __future__ import annotations
 
 import dataclasses
-import os
 from typing import Sequence
 
 import numpy as np
@@ -23,11 +22,11 @@ import numpy as np
 MAX_INPUTS = 4
 TARGET_BLOCKS = 4096  # >> 256 CUs * resident blocks, so the tail is short
 # geometry of the flat one-point-per-lane sweep (s1_xf1_kernel): threads per block, fewest elements per block
-FLAT1_THREADS = int(os.environ.get('WBX_FLAT1_THREADS', '256'))
-FLAT1_MIN_ELEMENTS = int(os.environ.get('WBX_FLAT1_MIN_ELEMENTS', '2816'))
+FLAT1_THREADS = 256
+FLAT1_MIN_ELEMENTS = 2816
 # ... and of its one-wave flavour (ens_pipe_kernel<.., FLAT>): elements per block, unless that leaves fewer blocks than this
-FLAT64_MIN_ELEMENTS = int(os.environ.get('WBX_FLAT64_MIN_ELEMENTS', '2816'))
-FLAT64_MIN_BLOCKS = int(os.environ.get('WBX_FLAT64_MIN_BLOCKS', '18432'))
+FLAT64_MIN_ELEMENTS = 2816
+FLAT64_MIN_BLOCKS = 18432
 
 
 @dataclasses.dataclass

@@ -16,11 +16,10 @@ Safety comes from refusing, not from guessing: a recording is only turned into a
     (-> relocated), or inside memory that the record itself keeps alive (plans, weights, atom tables, scratch, accumulator
     blocks, device blocks taken from the pool while recording -- those are pinned to the record).  One stray pointer -> no record;
   * no accumulator slot was created and nothing was summed on the host while recording.
-A chunk that cannot be replayed simply takes the ordinary path.  `WBX_CHUNK_REPLAY=0` turns the whole mechanism off (A/B)."""
+A chunk that cannot be replayed simply takes the ordinary path.  `replay.ENABLED = False` turns the whole mechanism off."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 import threading
 
 import numpy as np
@@ -28,7 +27,7 @@ import numpy as np
 from weatherbenchx_amd import _hip
 from weatherbenchx_amd import xarray_lite as xr
 
-ENABLED = os.environ.get('WBX_CHUNK_REPLAY', '1') != '0'
+ENABLED = True  # False: every chunk through the Python body instead of a replayed record (tests, tools/bench_replay.py)
 _MASK64 = (1 << 64) - 1
 TIME_DIMS = frozenset({'init_time', 'lead_time', 'valid_time', 'time'})
 STATS = {'recorded': 0, 'refused': 0, 'replayed': 0, 'refusals': []}  # (tests and tools read these)
