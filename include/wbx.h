@@ -71,16 +71,36 @@ typedef enum wbx_det_func { WBX_DET3 = 0, WBX_DET6 = 1, WBX_PASS1 = 2 } wbx_det_
  *  2 EnsembleVariance     var_m(p, ddof=1)
  *  3 UnbiasedEnsembleMeanSquaredError  (mean_m p - t)^2 - var/M
  *  4 SquaredError of the ensemble mean (mean_m p - t)^2   (EnsembleMean + SquaredError)
- * Accuracy per point against the float64 restatement of the float32 members (tests/test_gpu_round4.py holds these on outputs
- * of 64 points -- one tile -- and on whole fields; geopotential-like 5.5e4 +- 30, spread = 0.05 x error, a target at the
- * ensemble mean): the rank-form fp32 kernels for M = 50 / 51 (ens_pipe_kernel, ens_atoms_kernel) sum e = x - median in fp32
- * chains of <= 8 terms, every chain of non-negative terms:
- *   lanes 0, 1, 4   relative: <= 9 x 2^-24 = 5.4e-7 worst case, ~1e-7 typical
- *   lane 2          relative to S = sum e^2 / (M - 1) <= 3 var: |d var| <= 5.4e-7 S (the subtraction (sum e)^2 / M is fp64)
- *   lane 3          a DIFFERENCE, so its bound is absolute, in units of the two terms it is the difference of:
- *                   |d lane3| <= 1e-6 (lane 4 + lane 2 / M); relative 1e-6 wherever lane 3 is not itself a cancellation
- * Every other ensemble kernel (padded buckets, masked / skipna wrappers, pair form, generic) sums in fp64 on the widened
- * members: ~1e-15 (pair form: ~1e-7, its |x_i - x_j| row sums are fp32). */
+ * Accuracy per point against the float64 restatement of the float32 members.  tests/test_gpu_ensemble_points.py holds every
+ * line below per point, on every kernel that computes the lanes (wbx_ens_map, s1_xk / s1_xr / s1_xf1_kernel, ens_pipe_kernel and
+ * its FLAT flavour, the masked / skipna wrappers, ens_atoms_kernel), with the bounds computed per point from the inputs
+ * (tests/ensemble_cases.py); tests/test_gpu_round4.py holds outputs of 64 points and whole fields (geopotential-like
+ * 5.5e4 +- 30, spread = 0.05 x error, a target at the ensemble mean).  u = 2^-24, eps = 2^-52; e_i = x_i - s about the shift
+ * s of the kernel; A = mean |e_i|, Q = sum e_i^2 / (M - 1).
+ * The rank-form fp32 kernels for M = 50 / 51 (ens_pipe_kernel, ens_atoms_kernel) sum e = x - median in fp32 chains of <= 8
+ * terms, every chain of non-negative terms (s = the sorted median):
+ *   lanes 0, 1      relative: <= 9 u = 5.4e-7 worst case, ~1e-7 typical
+ *   lane 2          absolute: |d var| <= 9 u Q, Q <= 3 var (the subtraction (sum e)^2 / M is fp64)
+ *   lane 4          = (mean_m p - t)^2 is the square of a DIFFERENCE: bounded absolutely, not relatively.  The mean error
+ *                   carries d <= 9 u A, so |d lane4| <= 2 sqrt(lane 4) d + d^2; where the target sits near the ensemble mean
+ *                   the relative error of lane 4 is unbounded (0.2 on N(0, 1) members, 3e2 on a target within 1e-4 of the mean)
+ *   lane 3          a difference of lane 4 and lane 2 / M: |d lane3| <= (lane-4 bound) + (lane-2 bound) / M;
+ *                   <= 1e-6 (lane 4 + lane 2 / M) on physical fields (tests/test_gpu_round4.py)
+ * A point outside the fp32 range of these sums (member range not 0 and outside [2^-50, 2^60], a member or target magnitude above
+ * 2^100, an infinite target included) sends its whole 64-lane tile through the generic fp64 operator instead (wave-uniform; the
+ * tighter row below).  A NaN target does not: the magnitude test drops it (fmaxf) and the chains carry the NaN into lanes 0, 3, 4.
+ * Every other ensemble kernel sums in fp64 on the widened members: padded buckets, wrappers and wbx_ens_map (M = 50 / 51
+ * included) with s = the target, or the smallest member when the target is NaN / infinite; the generic operator (M > 64,
+ * float64) with s = the first member in memory, whatever the target is:
+ *   lane 0          relative (M + 4) eps;   lane 1  absolute 2 (M + 4) eps A (generic: relative (M + 4) eps);
+ *   lane 2          absolute (M + 6) eps Q; lane 4  as above with d = (M + 4) eps A (generic: (M + 4) eps A + 2 eps |s - t|);
+ *   lane 3          as above;   pair form (WBX_ENS_PAIRWISE, M <= 64): lane 1 relative (M + 1) u, its |x_i - x_j| rows are fp32.
+ * Members and targets that are not finite:
+ *   float32 rank form, M <= 64: a NaN OR INFINITE member makes all five lanes NaN.  Pair form, M > 64 and float64: plain IEEE
+ *   arithmetic of the formulas on e = x - s, the pairs summed over i > j -- one infinite member gives lanes 0, 1, 4 = +inf and
+ *   lanes 2, 3 = NaN (two of the same sign: lane 1 NaN too); on the generic operator an infinite FIRST member in memory is the
+ *   shift itself and turns lane 4 NaN as well.  A NaN / infinite target leaves lanes 1 and 2 finite on every route.
+ *   M = 1: lanes 2 and 3 are NaN (ddof = 1), the fair spread is NaN and the unfair spread 0. */
 #define WBX_ENS_LANES 5
 typedef enum wbx_ens_algo {
   WBX_ENS_SORT = 0,     /* rank / sorting-network form, probabilistic.py:214-240 (use_sort=True)  */

@@ -85,7 +85,7 @@ struct EnsOpGeneric {
     const double fair = (a.flags & WBX_FLAG_FAIR) ? 1.0 : 0.0;
     const double mean_e = se / dM;
     const double mean_d = (x0 - td) + mean_e;
-    const double var = (sq - se * mean_e) / (dM - 1.0);
+    const double var = (sq - se * mean_e) / (dM - 1.0);  // (one member: e = x0 - x0 = 0, so 0 / 0 = NaN as in the reference)
     val[0] = sabs / dM;
     val[1] = 2.0 * pair_total / (dM * (dM - fair));
     val[2] = var;
@@ -287,7 +287,8 @@ struct EnsOpF32 {
       // of the wave holds a point whose magnitudes could overflow / underflow an fp32 square or sum.  Then the CALLER redoes
       // the point with the generic fp64 op (members re-read from memory, a rolled loop: no registers of the hot path are
       // spent on the escape; a second set of unrolled fp64 sums here cost 20-40 VGPRs and a wave per SIMD).  Wave-uniform;
-      // never taken on physical fields.  The comparisons are false for NaN: a NaN target goes the same way.
+      // never taken on physical fields.  An infinite target goes the same way; a NaN target does not (fmaxf drops it): stats32
+      // carries it into the lanes that look at the target.
       const float range = xm[MP - 1] - xm[0];
       const float big = fmaxf(fmaxf(fabsf(xm[0]), fabsf(xm[MP - 1])), fabsf(r.t));
       const bool fast_ok = (range == 0.f || (range >= 0x1p-50f && range <= 0x1p60f)) && big <= 0x1p100f;
@@ -396,7 +397,9 @@ struct EnsOpF32 {
     // of the divisions of the float64 restatement.
     const double dM = (double)M;
     const double fair = (a.flags & WBX_FLAG_FAIR) ? 1.0 : 0.0;
-    const double inv_m = 1.0 / dM, inv_m1 = 1.0 / (dM - 1.0), spread_scale = 2.0 / (dM * (dM - fair));
+    // (a single member: ddof = 1 is 0 / 0 in the reference.  sq - se * mean_e is contracted to an FMA, which leaves the
+    //  rounding error of e^2 instead of 0, and that times 1 / 0 is +-inf: the NaN is stated, not left to the arithmetic)
+    const double inv_m = 1.0 / dM, inv_m1 = M > 1 ? 1.0 / (dM - 1.0) : __builtin_nan(""), spread_scale = 2.0 / (dM * (dM - fair));
     const double mean_e = se * inv_m;
     const double mean_d = x0t + mean_e;                       // mean_m p - t
     const double var = (sq - se * mean_e) * inv_m1;           // ddof = 1
