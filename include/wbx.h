@@ -365,6 +365,40 @@ int wbx_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* 
                             const void* p, const void* t, const double* thresholds /* DEVICE float64[nthr] */,
                             const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: ranked probability score of an ensemble at a list of thresholds (joined ABI 13) ----------------
+ * EnsembleRankedProbabilityScore (probabilistic.py:339-477) of an ensemble of predictions against a scalar target, in one pass
+ * over p and t: no [nthr][M][frame] indicator arrays of the two ContinuousToCDF transforms (wrappers.py) are formed.  p has a
+ * member axis of length M and element stride `member_stride` that is not part of key / depth / x, as for wbx_ens_partial.
+ * Per point, with members x_m, target y, prediction thresholds a_k = p_thresholds[k], target thresholds b_k = t_thresholds[k]:
+ *     c_k = #{m : (double)x_m <= a_k},  o_k = [(double)y <= b_k]       (`<` instead of `<=` when right_inclusive == 0)
+ *     WBX_FLAG_FAIR:  n_k = (M - 1) (c_k - o_k M)^2 - c_k (M - c_k),  D = M^2 (M - 1)   [(mean - o)^2 - var(ddof = 1) / M]
+ *     otherwise:      n_k = (c_k - o_k M)^2,                          D = M^2           [(mean - o)^2]
+ *     value = (sum_k n_k) / D
+ * Everything is a function of the integers c_k: the kernel sorts nothing and adds no floating-point numbers.  A partial is the
+ * signed 64-bit sum S of sum_k n_k over its points, written once as (double)S / (double)D -- the correctly rounded quotient of
+ * two integers, a function of the inputs and the plan only, bit for bit, whatever the order of summation.
+ * ONE value lane.  Count lanes follow the library's convention (none / one shared / one per value lane).  A point with a NaN
+ * member or a NaN target is a NaN statistic (sum(bin_dim, skipna=False) of NaN terms): without flags it poisons its partial;
+ * under WBX_FLAG_MASKED alone it contributes exactly 0 where the mask is 0 and poisons where it is not; under WBX_FLAG_SKIPNA it
+ * is counted out.  -0.0 <= 0.0 is true; +-inf members and targets compare as IEEE says.
+ * partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial: wbx_s1_partial_len with lanes = 1, wbx_contract and
+ * wbx_contract_bits serve it unchanged.
+ * `p_thresholds` / `t_thresholds` are DEVICE float64[nthr] each; they need not be sorted or distinct, +-inf is allowed.  NaN
+ * thresholds are the caller's business: a comparison with one is false here, while the reference makes the point NaN.
+ * float32 inputs are compared in float32 against the threshold rounded to float32 toward -inf for `<=` and toward +inf for
+ * `<`, which decides exactly like the float64 comparison for every float32 value (+-inf and thresholds beyond the float32
+ * range included; rounding to nearest would not: float(0.1) <= 0.1 is false).
+ * Refused (WBX_ERR_INVALID, output untouched): nthr outside 1..WBX_ERPS_MAX_THRESHOLDS, M outside 1..WBX_ERPS_MAX_MEMBERS,
+ * WBX_FLAG_FAIR with M < 2, an unknown dtype, flags beyond MASKED | SKIPNA | FAIR, WBX_FLAG_MASKED with a NULL mask,
+ * plane_rows != 0 or x_weights, and depth_chunk * nx * nthr * (M - 1) * M^2 >= 2^53 (S must stay exact in fp64).  vec = 4 is
+ * accepted and read with dword loads (a lane owns a point and walks its members: the wave's load of one member row is
+ * coalesced as it is).  nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_ERPS_MAX_THRESHOLDS 16 /* per launch */
+#define WBX_ERPS_MAX_MEMBERS 256   /* sum_k n_k of a point fits an int32 */
+int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                        int nthr, const double* p_thresholds, const double* t_thresholds /* DEVICE float64[nthr] each */,
+                        int right_inclusive, const void* p, const void* t, const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -573,7 +607,7 @@ typedef enum wbx_fn {
   WBX_FN_CONTRACT = 6, WBX_FN_CONTRACT_BITS = 7, WBX_FN_DET_BINNED = 8, WBX_FN_ENS_BINNED = 9, WBX_FN_ZONAL_SPECTRUM = 10,
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
-  WBX_FN_CONTINGENCY_PARTIAL = 20
+  WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -444,6 +444,16 @@ def contingency_available(ctx) -> bool:
     return False
 
 
+def ens_rps_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_rps_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_rps_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -743,6 +753,12 @@ def _run_s1(ctx, kind: str, dplan: _PlanOnDevice, plan: planner.S1Plan, devs: Se
       _hip.check(ctx.lib.wbx_contingency_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(nthr), ptr(devs[0]),
                                                  ptr(devs[1]), ptr(thr), ptr(devs[3]), C.c_void_p(out.ptr)),
                  'wbx_contingency_partial')
+    elif kind == 'erps':
+      m, mstride = ens
+      nthr, p_thr, t_thr, right = cat
+      _hip.check(ctx.lib.wbx_ens_rps_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(m), int(mstride), int(nthr),
+                                             ptr(p_thr), ptr(t_thr), int(bool(right)), ptr(devs[0]), ptr(devs[1]), ptr(devs[3]),
+                                             C.c_void_p(out.ptr)), 'wbx_ens_rps_partial')
     elif kind == 'cat':
       cfunc, ncat, m, mstride, thr, _ = cat
       _hip.check(ctx.lib.wbx_cat_partial(ctx.handle, C.byref(dplan.struct), int(cfunc), dtype_code, int(ncat), int(m),
@@ -1438,7 +1454,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   kind 'det' / 'ens' / 'cat' (indicator statistics: `cat` = {'func', 'ncat', 'thresholds' (float64 ndarray or None),
   'member_dim' (or None), 'M'}; one value lane per category) / 'cont' (thresholded contingency tables,
   wbx_contingency_partial: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
-  cell * nthr + k, cell in (TP, FP, FN, TN)).
+  cell * nthr + k, cell in (TP, FP, FN, TN)) / 'erps' (ranked probability score of an ensemble, wbx_ens_rps_partial: `cat` =
+  {'p_thresholds', 't_thresholds' (float64 ndarrays of equal size, at most _hip.ERPS_MAX_THRESHOLDS), 'right_inclusive'},
+  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1509,6 +1527,14 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
     if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
       raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
     nl = _hip.CONT_CELLS * nthr
+  if kind == 'erps':
+    nthr = int(np.asarray(cat['p_thresholds']).size)
+    if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS or int(np.asarray(cat['t_thresholds']).size) != nthr:
+      raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} prediction and as many target thresholds '
+                       f"(got {nthr} and {int(np.asarray(cat['t_thresholds']).size)})")
+    if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
+      raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
+    nl = 1
   counted = bool(flags & 3)
   shared_count = counted and not (flags & _hip.FLAG_SKIPNA)  # mask only: one count lane for every statistic
   nl_total = nl + 1 if shared_count else nl * (2 if counted else 1)
@@ -1528,12 +1554,17 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   if kind == 'cont':
     cont_thr = _threshold_table(ctx, cat['thresholds'])
     cat_args = (nthr, cont_thr)
+  erps_thr = (None, None)
+  if kind == 'erps':
+    erps_thr = (_threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']))
+    ens_args = (ens['M'], devs[0].layout.stride(member_dim))
+    cat_args = (nthr, erps_thr[0], erps_thr[1], bool(cat['right_inclusive']))
   w_buf = _device_w(ctx, plan, w_da, bin_dims)
   # (a chunk that is being recorded: the record keeps what the launches below point at -- plan tables, weights / bins / atom
   #  tables, inputs that do not follow the chunk such as the climatology, threshold tables)
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
-  replay.keep(dplan, w_buf, cont_thr if kind == 'cont' else (cat_args[4] if cat_args else None),
+  replay.keep(dplan, w_buf, cont_thr if kind == 'cont' else (cat_args[4] if cat_args and kind == 'cat' else None), *erps_thr,
               devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None)
   bin_shape = w_buf.bin_shape
   s2 = planner.build_s2_plan(plan, nl_total, w_buf.shape[-1])

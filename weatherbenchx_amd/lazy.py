@@ -43,6 +43,9 @@ def cat_lanes_per_launch(func: int, masked: bool, skipna: bool) -> int:
 # False (WBX_FUSED_CONTINGENCY=0): thresholded contingency tables (categorical.TruePositives .. behind wrappers.ContinuousToBinary)
 # are materialised and reduced on the host route as before wbx_contingency_partial existed (A/B timing and tests).
 FUSED_CONTINGENCY = os.environ.get('WBX_FUSED_CONTINGENCY', '1') != '0'
+# False (WBX_FUSED_ENS_RPS=0): probabilistic.EnsembleRankedProbabilityScore builds the [K, M, frame] indicator arrays of its two
+# ContinuousToCDF transforms on the host and reduces them as before wbx_ens_rps_partial existed (A/B timing and tests).
+FUSED_ENS_RPS = os.environ.get('WBX_FUSED_ENS_RPS', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -205,7 +208,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps'):
       return [self.p, self.t], 0
     if self.clim is not None:
       return [self.p, self.t, self.clim.source], _hip.DET6
@@ -224,6 +227,9 @@ class FusedGroup:
       return self._reduce_cat(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
     if self.kind == 'cont':
       return self._reduce_cont(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
+    if self.kind == 'erps':  # one value lane, one launch (wbx_ens_rps_partial): fair / inclusive are the group's own
+      return engine.reduce_statistics('erps', inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
+                                      bin_dims, mask=mask, skipna=skipna, ens=self.ens, cat=self.cat)
     return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
                                bin_dims, func=func, mask=mask, skipna=skipna, clim=self.clim, ens=ens)
 
@@ -292,6 +298,16 @@ class FusedGroup:
     return memo[block]
 
   def materialise(self, lane: int, ens_params=None) -> np.ndarray:
+    if self.kind == 'erps':
+      # the per-point values are the host route's, bit for bit (the indicator arrays of the two ContinuousToCDF transforms and
+      # labelled-array arithmetic on them): whoever reads them sees what it saw before the fused reduction existed
+      from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
+      cat = self.cat
+      stat = multivariate.EnsembleRankedProbabilityScore(
+          cat['p_values'], cat['t_values'], cat['bin_dim'], '', ensemble_dim=self.ens['member_dim'], skipna_ensemble=False,
+          fair=self.ens['fair'], enforce_monotonicity=False, right_inclusive=cat['right_inclusive'])
+      out = stat.host_per_variable(self.p, self.t)
+      return out.transpose(*self.dims).data
     if self.kind == 'ens2':  # stage 1 with every dim kept IS the per-point statistic
       with engine.synchronous_results():
         values, _, out_dims = self.reduce((), None, (), use_mask=False, skipna=False)
@@ -684,6 +700,32 @@ def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr
   cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim}
   grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
   return LazyContingency(grp, cell, threshold_dim, name=p.name)
+
+
+def ens_rps_statistic(p, t, ensemble_dim: str, p_thr, t_thr, fair: bool, right_inclusive: bool, bin_dim: str = 'bin') -> xr.DataArray:
+  """EnsembleRankedProbabilityScore of the ensemble `p` against the scalar-valued `t` as a LazyStatistic (lane 0) on a FusedGroup of
+  kind 'erps'.  `p_thr` / `t_thr`: plain sequences of as many real numbers, prediction and target thresholds.  The (p, t) objects,
+  the bytes of both tables, `fair` and `right_inclusive` key the group; its frame drops the member dim.  `bin_dim` only names
+  the threshold dim of the host route behind `.data`, which sums it away."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if ensemble_dim not in p.dims:
+    raise ValueError(f'Dimension {ensemble_dim} not found in {p.dims}')
+  if ensemble_dim in t.dims:
+    raise ValueError(f'targets must not carry {ensemble_dim!r} here')
+  p_values, t_values = list(p_thr), list(t_thr)
+  pa, tb = np.asarray(p_values, np.float64).reshape(-1), np.asarray(t_values, np.float64).reshape(-1)
+  if pa.size != tb.size:
+    raise ValueError(f'{pa.size} prediction thresholds against {tb.size} target thresholds')
+  ckey = ('erps', pa.tobytes(), tb.tobytes(), bool(fair), bool(right_inclusive), bin_dim)
+  table = p.__dict__.get('_wbx_groups')
+  if not (table and any(k[0] == 'erps' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and k[3] == ensemble_dim
+                        and v[0]() is t and v[1]() is not None for k, v in table.items())):
+    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier statistic has checked their frames)
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': bool(fair)}
+  cat = {'p_thresholds': pa, 't_thresholds': tb, 'right_inclusive': bool(right_inclusive), 'p_values': p_values,
+         't_values': t_values, 'bin_dim': bin_dim}
+  grp = _group_for('erps', p, t, ens=ens, clim_key=ckey, cat=cat)
+  return LazyStatistic(grp, 0, name=p.name)
 
 
 ENS2_LANE = {'CRPSSkill': 0, 'UnbiasedEnsembleMeanSquaredError': 1}

@@ -49,7 +49,7 @@ class _Indicator(base.PerVariableStatistic):
       return None
     if transform.which != 'both':
       return None
-    values = _plain_thresholds(transform._threshold_value)  # pylint: disable=protected-access
+    values = wrappers.plain_thresholds(transform._threshold_value)  # pylint: disable=protected-access
     dim = transform._threshold_dim  # pylint: disable=protected-access
     if values is None:
       return None
@@ -63,21 +63,6 @@ class _Indicator(base.PerVariableStatistic):
         return None
       pairs[name] = (p, t)
     return {name: lazy.contingency_statistic(_CELL_INDEX[type(self)], p, t, dim, values) for name, (p, t) in pairs.items()}
-
-
-def _plain_thresholds(values):
-  """The thresholds as a list when they are a plain sequence of real numbers that float64 holds exactly, else None."""
-  if not isinstance(values, (list, tuple, np.ndarray)) or len(values) == 0 or (isinstance(values, np.ndarray) and values.ndim != 1):
-    return None
-  out = list(values)
-  for v in out:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-      return None
-    if isinstance(v, (int, np.integer)) and int(float(v)) != int(v):
-      return None
-    if isinstance(v, np.floating) and v.dtype.itemsize > 8:
-      return None
-  return out
 
 
 class TruePositives(_Indicator):

@@ -5,6 +5,9 @@ None of these is on the path SURVEY section 8 names and none has a kernel of its
 arithmetic on whatever holds the payload (NumPy on the host, torch where a chunk is resident in HBM), and their weighted, binned,
 masked means are the Aggregator's reduction -- the same kernels as every other statistic.  `metrics.probabilistic` hands these
 names on, so `probabilistic.EnergyScore` etc. resolve as in the reference.
+
+One exception: EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own,
+wbx_ens_rps_partial (lazy.ens_rps_statistic); its per-point values are still this arithmetic.
 """
 from __future__ import annotations
 
@@ -12,6 +15,9 @@ from typing import Mapping
 
 import numpy as np
 
+from weatherbenchx_amd import _hip
+from weatherbenchx_amd import engine
+from weatherbenchx_amd import lazy
 from weatherbenchx_amd import xarray_lite as xr
 from weatherbenchx_amd.metrics import base
 from weatherbenchx_amd.metrics import categorical
@@ -44,6 +50,9 @@ class EnsembleRankedProbabilityScore(base.PerVariableStatistic):
     self._fair = fair
     self._bin_dim = bin_dim
     self._unique_name_suffix = unique_name_suffix
+    self._thresholds = (prediction_bin_thresholds, target_bin_thresholds)
+    self._enforce_monotonicity = enforce_monotonicity
+    self._right_inclusive = right_inclusive
     cdf = {which: wrappers.ContinuousToCDF(which=which, threshold_values=values, threshold_dim=bin_dim,
                                            unique_name_suffix=unique_name_suffix, enforce_monotonicity=enforce_monotonicity,
                                            right_inclusive=right_inclusive)
@@ -64,8 +73,46 @@ class EnsembleRankedProbabilityScore(base.PerVariableStatistic):
             f'{self._unique_name_suffix}')
 
   def _compute_per_variable(self, predictions, targets):
+    fused = self._fused_per_variable(predictions, targets)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The score from the indicator arrays of the two ContinuousToCDF transforms, on the host."""
     squared = self._per_threshold.compute({'_': predictions}, {'_': targets})['_']
     return xr.as_dataarray(squared).sum(self._bin_dim, skipna=self._skipna_ensemble)
+
+  def _fused_per_variable(self, predictions, targets):
+    """The score as a lazy statistic that the Aggregator reduces with one launch of wbx_ens_rps_partial (lazy.ens_rps_statistic),
+    or None when the combination is not the plain one: numbers for thresholds, an ensemble of predictions against scalar-valued
+    targets, no per-point member counts.  Reading the statistic's values still computes them on the host."""
+    if not lazy.FUSED_ENS_RPS or self._skipna_ensemble:
+      return None
+    pa, tb = (wrappers.plain_thresholds(v) for v in self._thresholds)
+    if pa is None or tb is None or len(pa) != len(tb) or len(pa) > _hip.ERPS_MAX_THRESHOLDS:
+      return None
+    fa, fb = np.asarray(pa, np.float64), np.asarray(tb, np.float64)
+    if np.isnan(fa).any() or np.isnan(fb).any():
+      return None
+    if not np.array_equal(np.asarray(pa), np.asarray(tb)):
+      return None  # (two lists label the threshold dim differently: the host route joins them on the labels they share)
+    p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+    e = self._ensemble_dim
+    if e not in p.dims or e in t.dims or self._bin_dim in p.dims or self._bin_dim in t.dims or not set(t.dims) <= set(p.dims):
+      return None
+    if str(p.dtype) not in ('float32', 'float64') or str(t.dtype) not in ('float32', 'float64'):
+      return None
+    m = p.sizes[e]
+    if m > _hip.ERPS_MAX_MEMBERS or (self._fair and m < 2):
+      return None
+    if self._enforce_monotonicity and not (np.all(np.diff(fa) > 0) and np.all(np.diff(fb) > 0)):
+      return None  # (the host route raises)
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on (the host route says so where it needs one)
+      return None
+    if not engine.ens_rps_available(ctx):
+      return None
+    return lazy.ens_rps_statistic(p, t, e, pa, tb, self._fair, self._right_inclusive, bin_dim=self._bin_dim)
 
 
 class EnergyScoreSkill(base.PerVariableStatistic):

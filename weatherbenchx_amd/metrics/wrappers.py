@@ -455,6 +455,21 @@ def select_bin_thresholds_by_time_from_chunk(bin_thresholds: xr.DataArray, chunk
   return bt
 
 
+def plain_thresholds(values):
+  """The thresholds as a list when they are a plain sequence of real numbers that float64 holds exactly, else None."""
+  if not isinstance(values, (list, tuple, np.ndarray)) or len(values) == 0 or (isinstance(values, np.ndarray) and values.ndim != 1):
+    return None
+  out = list(values)
+  for v in out:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+      return None
+    if isinstance(v, (int, np.integer)) and int(float(v)) != int(v):
+      return None
+    if isinstance(v, np.floating) and v.dtype.itemsize > 8:
+      return None
+  return out
+
+
 def compute_cdf(threshold_values, da: xr.DataArray, threshold_dim: str, enforce_monotonicity: bool, right_inclusive: bool = True) -> xr.DataArray:
   """[x <= threshold] (or <) for every threshold as float, NaN where x or the threshold is NaN (wrappers.py:349-390)."""
   da = xr.as_dataarray(da)
