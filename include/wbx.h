@@ -311,7 +311,10 @@ int wbx_contract(wbx_ctx* ctx, const wbx_s2_plan* plan, const double* partial,
 
 /* Same contraction for W = wt[Bk][Br][j] * mask[Bk][Br][j][bin] with BOOLEAN masks and nbin <= 64 (Regions / LandSea
  * binning, binning.py:92-201, times GridAreaWeighting): `wt` is float64[nBk][nBr][nj]; bit b of bits[nBk][nBr][nj]
- * says whether the point belongs to bin b.  Result layout and NaN semantics are identical to wbx_contract. */
+ * says whether the point belongs to bin b.  Result layout and NaN semantics are identical to wbx_contract, with one exception: an
+ * INFINITE partial makes its lane NaN in EVERY bin of the cell -- the kernel adds (partial * w) * 0 to every bin, which is NaN
+ * for +-inf as it is for NaN -- where wbx_contract (and the reference's xr.dot) keep +-inf in the bins the point belongs to and
+ * give NaN only in the others. */
 int wbx_contract_bits(wbx_ctx* ctx, const wbx_s2_plan* plan, const double* partial, const double* wt,
                       const uint64_t* bits, double* out);
 
@@ -408,7 +411,18 @@ int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_
  * weights come factored: WBX_BINNED_WT_X_ONLY -> wt[nBk][nx] (GridAreaWeighting, weighting.py:62-130, on
  * latitude-fastest chunks), WBX_BINNED_WT_ROW_ONLY -> wt[nBk][nBr] (the same on longitude-fastest chunks); `bits` keeps
  * its full index either way.  out[nA][nBk][lanes_total][nbin], lanes_total and NaN semantics exactly as
- * wbx_det_partial + wbx_contract_bits.  The plan's nchunk / x_kept / vec are ignored. */
+ * wbx_det_partial + wbx_contract_bits.  The plan's nchunk / x_kept / vec are ignored.
+ * `wt` must not be NULL (WBX_ERR_INVALID; wbx_ens_binned takes NULL as ones, this entry point does not).  An x stride that is
+ * negative, or with which a row spans 2^31 bytes or more, in any input sends EVERY patch through the slot kernel (det_binned_kernel:
+ * about half the speed; the atom kernel addresses a row as a uniform base plus an unsigned 32-bit lane offset).
+ * Non-finite statistics: a NaN statistic under a valid point makes its lane NaN in every bin of its (A, Bk) cell, whatever the
+ * point's weight or membership (a zero weight, a point in no bin), as the reference's xr.dot does; so does an INFINITE statistic
+ * (+-inf * 0 of the sum it went into is added to every bin), where the reference keeps +-inf in the bins the point belongs to.
+ * Accuracy of every output against the float64 restatement of the widened inputs (the lanes above, each term the rounded product
+ * lane * wt, summed exactly): |d out| <= (N + 4) eps / 2 * sum |wt_i lane_i| over the N valid points of the cell inside the bin,
+ * eps = 2^-52, in any order of the sums (atom or slot kernel, prepared tables or not), count lanes included; integer-valued lanes
+ * under unit weights are exact.  tests/test_gpu_det_binned.py holds every output of every mode (DET3 / DET6 / PASS1 x mask modes x
+ * weight layouts x float32 / float64), route and edge to that bound, computed per output from the inputs (tests/det_binned_cases.py). */
 #define WBX_BINNED_W_ON_X 1
 #define WBX_BINNED_WT_X_ONLY 2
 #define WBX_BINNED_WT_ROW_ONLY 4
