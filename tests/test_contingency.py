@@ -355,6 +355,22 @@ def test_more_thresholds_than_a_launch_takes(fused):
     np.testing.assert_allclose(np.asarray(values[key].values), np.asarray(values0[key].values), rtol=1e-11, atol=1e-11, equal_nan=True)
 
 
+def test_more_thresholds_than_a_launch_takes_with_an_empty_kept_dim(fused):
+  """The blocks are joined by their sizes, not by what is left over: a kept dim of length 0 leaves nothing over."""
+  nthr = _hip.CONT_MAX_THRESHOLDS + 3
+  thresholds = list(np.round(np.random.default_rng(3).gamma(2.0, size=nthr), 3))
+  pred, targ = _inputs(shape=(3, 0, 10))
+  agg = lambda: aggregation.Aggregator(reduce_dims=['time', 'longitude'])
+  _, state, values = _evaluate(METRICS(thresholds), pred, targ, agg())
+  assert [e['nthr'] for e in _launches()] == [_hip.CONT_MAX_THRESHOLDS, 3]
+  fused.setattr(lazy, 'FUSED_CONTINGENCY', False)
+  _, state0, values0 = _evaluate(METRICS(thresholds), pred, targ, agg())
+  _assert_states_equal(state, state0)
+  assert values and set(values) == set(values0)
+  for key in values:
+    assert values[key].shape == values0[key].shape and 0 in values[key].shape and nthr in values[key].shape, (key, values[key].shape)
+
+
 def test_threshold_dim_reduced_or_weighted_takes_the_host_route(fused):
   pred, targ = _inputs()
   metrics = METRICS()

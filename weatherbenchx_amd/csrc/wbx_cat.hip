@@ -173,46 +173,31 @@ __global__ void __launch_bounds__(64) s1_cat_kernel(S1Args a, CatArgs c, int nac
 namespace wbx {
 static int cat_common(wbx_ctx* ctx, const wbx_s1_plan* plan, int func, int dtype, int ncat, int M, int64_t member_stride, const void* p,
                       const void* t, const double* thresholds, bool field, int64_t cat_stride, const uint8_t* mask, double* partial_out) {
-  WBX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
+  if (int rc = s1_begin("", ctx, plan)) return rc;
   WBX_REQUIRE(func == WBX_CAT_EXCEED || func == WBX_CAT_RANK, "unknown categorical family %d", func);
   WBX_REQUIRE(ncat >= 1 && ncat <= 256, "1..256 categories (got %d)", ncat);
   WBX_REQUIRE(M >= 1, "M must be >= 1");
   if (func == WBX_CAT_RANK) WBX_REQUIRE(ncat == M + 1, "rank histogram needs ncat == M + 1");
-  const int nacc = ncat + ((plan->flags & WBX_FLAG_SKIPNA) ? ncat : ((plan->flags & WBX_FLAG_MASKED) ? 1 : 0));
+  const int nacc = (int)partial_lanes(plan->flags, ncat);
   const bool rank = func == WBX_CAT_RANK;
   const size_t counter = rank ? sizeof(uint32_t) : sizeof(double);
   WBX_REQUIRE((size_t)nacc * 64 * counter <= 64 * 1024, "too many categories for the LDS columns (%d lanes)", nacc);
   if (rank)  // a thread's counters are uint32: it meets at most depth_chunk * ceil(nx / 64) points
     WBX_REQUIRE((double)plan->depth_chunk * (double)((plan->nx + 63) / 64) < 4.0e9, "rank histogram: more than 2^32 points per thread");
-  if (plan->nkey == 0) return 0;
-  WBX_REQUIRE(partial_out != nullptr, "partial_out is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
-  const int64_t nj = plan->x_kept ? plan->nx : 1;
-  if (plan->ndepth == 0 || plan->nx == 0) {
-    const size_t n = (size_t)plan->nkey * plan->nchunk * nacc * (size_t)nj;
-    if (n) WBX_HIP(hipMemsetAsync(partial_out, 0, n * sizeof(double), ctx->stream));
-    return 0;
-  }
-  WBX_REQUIRE(p != nullptr && t != nullptr, "p/t is NULL");
-  if (func == WBX_CAT_EXCEED) WBX_REQUIRE(thresholds != nullptr, "thresholds is NULL");
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "WBX_FLAG_MASKED set but mask is NULL");
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
-  a.in[3] = mask;
+  if (int rc = s1_operands({"", "partial_out", "p/t"}, ctx, plan, 2, p, t, mask, partial_out, a, false)) return rc;
+  bool done;
+  if (int rc = s1_zero_if_empty(ctx, plan, nacc, partial_out, &done); rc || done) return rc;
+  if (func == WBX_CAT_EXCEED) WBX_REQUIRE(thresholds != nullptr, "thresholds is NULL");
   a.M = M;
   a.mstride = member_stride;
-  a.out = partial_out;
   CatArgs c;
   c.thr = thresholds;
   c.cstride = cat_stride;
   c.ncat = ncat;
   c.func = func;
-  a.nxtile = (int)((plan->nx + 63) / 64);
-  const int64_t grid = plan->nkey * plan->nchunk * (plan->x_kept ? a.nxtile : 1);
-  WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
+  int64_t grid;
+  if (int rc = s1_grid(plan, plan->x_kept ? 64 : 0, a, &grid)) return rc;
   const size_t lds = (size_t)nacc * 64 * counter;
 #define WBX_LAUNCH_CAT(TT, MFIX)                                                                                              \
   do {                                                                                                                        \

@@ -87,6 +87,12 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
+  return v;
+}
+
 // Sum over the 64 lanes with DPP row operations (no LDS crossbar round trips, unlike the ds_bpermute shuffles above):
 // the total is valid in LANE 63 ONLY.  All lanes must be active.  Same step pattern as wave_or32 (wbx_patch.hpp).
 template <int CTRL, int ROW_MASK>

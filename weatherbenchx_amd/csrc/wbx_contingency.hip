@@ -238,35 +238,14 @@ __global__ void __launch_bounds__(256) cont_xk_kernel(S1Args a, const double* th
     if (q < nthr) cont_write(o, a.nx, nthr, q, a.flags, ctp[q], cp[q], co[q], ngood, nvalid);
 }
 
-template <typename T, int NT, bool MASKED>
-static int cont_launch(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const double* thr, int nthr, int nacc) {
-  if (plan->x_kept) {
-    a.nxtile = (int)((plan->nx + plan->block_threads - 1) / plan->block_threads);
-    const int64_t grid = plan->nkey * a.nxtile * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
-    hipLaunchKernelGGL((cont_xk_kernel<T, NT, MASKED>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, thr, nthr,
-                       nacc);
-  } else {
-    const int64_t grid = plan->nkey * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
-    if (plan->vec == 4)
-      hipLaunchKernelGGL((cont_xr_kernel<T, 4, NT, MASKED>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, thr,
-                         nthr, nacc);
-    else
-      hipLaunchKernelGGL((cont_xr_kernel<T, 1, NT, MASKED>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, thr,
-                         nthr, nacc);
-  }
-  WBX_HIP(hipGetLastError());
-  return 0;
-}
-
-// the kernels are built for 1, 4, 8 and 16 threshold slots; a launch takes the smallest that holds nthr
 template <typename T, bool MASKED>
 static int cont_dispatch(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const double* thr, int nthr, int nacc) {
-  if (nthr <= 1) return cont_launch<T, 1, MASKED>(ctx, plan, a, thr, nthr, nacc);
-  if (nthr <= 4) return cont_launch<T, 4, MASKED>(ctx, plan, a, thr, nthr, nacc);
-  if (nthr <= 8) return cont_launch<T, 8, MASKED>(ctx, plan, a, thr, nthr, nacc);
-  return cont_launch<T, WBX_CONT_MAX_THRESHOLDS, MASKED>(ctx, plan, a, thr, nthr, nacc);
+  return dispatch_slots(nthr, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    const auto xk = cont_xk_kernel<T, NT, MASKED>;  // (named ahead of the ?: below: the code object keeps the kernels in the order they are named)
+    return launch_xk_or_xr(ctx, plan, a, xk, plan->vec == 4 ? cont_xr_kernel<T, 4, NT, MASKED> : cont_xr_kernel<T, 1, NT, MASKED>, thr,
+                           nthr, nacc);
+  });
 }
 
 }  // namespace wbx
@@ -274,37 +253,23 @@ static int cont_dispatch(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const
 extern "C" int wbx_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype, int nthr, const void* p, const void* t,
                                        const double* thresholds, const uint8_t* mask, double* partial_out) {
   using namespace wbx;
-  static_assert(WBX_CONT_MAX_THRESHOLDS == 16, "cont_dispatch's largest instantiation");
-  WBX_REQUIRE(ctx != nullptr, "wbx_contingency_partial: ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
+  const S1Names names = {"wbx_contingency_partial: ", "partial_out", "p/t"};
+  if (int rc = s1_begin(names.who, ctx, plan)) return rc;
   WBX_REQUIRE(nthr >= 1 && nthr <= WBX_CONT_MAX_THRESHOLDS, "wbx_contingency_partial: 1..%d thresholds per launch (got %d)",
               WBX_CONT_MAX_THRESHOLDS, nthr);
   WBX_REQUIRE(dtype == WBX_F32 || dtype == WBX_F64, "wbx_contingency_partial: unknown dtype %d", dtype);
   WBX_REQUIRE(!(plan->flags & ~(WBX_FLAG_MASKED | WBX_FLAG_SKIPNA)), "wbx_contingency_partial: flags other than MASKED | SKIPNA (0x%x)",
               plan->flags);
   WBX_REQUIRE(plan->plane_rows == 0 && plan->x_weights == nullptr, "wbx_contingency_partial: no plane mode, no folded x weights");
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "wbx_contingency_partial: WBX_FLAG_MASKED set but mask is NULL");
   // uint32 counters: a partial meets at most depth_chunk * nx points
   WBX_REQUIRE((double)plan->depth_chunk * (double)(plan->nx > 0 ? plan->nx : 1) < 4294967296.0,
               "wbx_contingency_partial: 2^32 or more points per partial (depth_chunk * nx)");
-  if (plan->nkey == 0) return 0;
-  WBX_REQUIRE(partial_out != nullptr, "wbx_contingency_partial: partial_out is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
-  const int nl = WBX_CONT_CELLS * nthr;
-  const int nacc = (plan->flags & WBX_FLAG_SKIPNA) ? 2 * nl : ((plan->flags & WBX_FLAG_MASKED) ? nl + 1 : nl);
-  if (plan->ndepth == 0 || plan->nx == 0) {  // empty reduction: the sums are zero
-    const size_t n = (size_t)plan->nkey * plan->nchunk * nacc * (size_t)(plan->x_kept ? plan->nx : 1);
-    if (n) WBX_HIP(hipMemsetAsync(partial_out, 0, n * sizeof(double), ctx->stream));
-    return 0;
-  }
-  WBX_REQUIRE(p != nullptr && t != nullptr, "wbx_contingency_partial: p/t is NULL");
-  WBX_REQUIRE(thresholds != nullptr, "wbx_contingency_partial: thresholds is NULL");
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
-  a.in[3] = mask;
-  a.out = partial_out;
+  if (int rc = s1_operands(names, ctx, plan, 2, p, t, mask, partial_out, a)) return rc;
+  const int nacc = (int)partial_lanes(plan->flags, WBX_CONT_CELLS * nthr);
+  bool done;
+  if (int rc = s1_zero_if_empty(ctx, plan, nacc, partial_out, &done); rc || done) return rc;
+  WBX_REQUIRE(thresholds != nullptr, "wbx_contingency_partial: thresholds is NULL");
   const bool masked = plan->flags & WBX_FLAG_MASKED;
   if (dtype == WBX_F32)
     return masked ? cont_dispatch<float, true>(ctx, plan, a, thresholds, nthr, nacc)

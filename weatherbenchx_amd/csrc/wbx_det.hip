@@ -244,21 +244,12 @@ static int dispatch_func(wbx_ctx* ctx, const wbx_s1_plan* plan, int func, S1Args
 
 static int det_common(wbx_ctx* ctx, const wbx_s1_plan* plan, int func, int dtype, const void* p, const void* t,
                       const void* c, const uint8_t* mask, double* out, bool map, int lane) {
-  WBX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
-  WBX_REQUIRE(out != nullptr || plan->nkey == 0, "output pointer is NULL");
-  WBX_REQUIRE(p != nullptr || plan->nkey * plan->ndepth * plan->nx == 0, "predictions pointer is NULL");
+  if (int rc = s1_begin("", ctx, plan)) return rc;
   if (func != WBX_PASS1) WBX_REQUIRE(t != nullptr || plan->nkey * plan->ndepth * plan->nx == 0, "targets pointer is NULL");
   if (func == WBX_DET6) WBX_REQUIRE(c != nullptr || plan->nkey * plan->ndepth * plan->nx == 0, "climatology pointer is NULL");
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "WBX_FLAG_MASKED set but mask is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
+  if (int rc = s1_operands({"", "output pointer", "predictions pointer"}, ctx, plan, 1, p, t, mask, out, a)) return rc;
   a.in[2] = c;
-  a.in[3] = mask;
-  a.out = out;
   a.lane = lane;
   if (dtype == WBX_F32) return dispatch_func<float>(ctx, plan, func, a, map);
   if (dtype == WBX_F64) return dispatch_func<double>(ctx, plan, func, a, map);
@@ -281,9 +272,6 @@ extern "C" int wbx_det_map(wbx_ctx* ctx, const wbx_s1_plan* plan, int func, int 
 
 extern "C" int wbx_s1_partial_len(const wbx_s1_plan* plan, int lanes, int64_t* n_out) {
   if (!plan || !n_out || lanes <= 0) return wbx::fail(WBX_ERR_INVALID, "bad arguments to wbx_s1_partial_len");
-  const int64_t nj = plan->x_kept ? plan->nx : 1;
-  const int64_t nl = (plan->flags & WBX_FLAG_SKIPNA) ? 2 * (int64_t)lanes
-                     : ((plan->flags & WBX_FLAG_MASKED) ? (int64_t)lanes + 1 : (int64_t)lanes);
-  *n_out = plan->nkey * plan->nchunk * nl * nj;
+  *n_out = plan->nkey * plan->nchunk * wbx::partial_lanes(plan->flags, lanes) * (plan->x_kept ? plan->nx : 1);
   return 0;
 }

@@ -7,24 +7,14 @@ namespace wbx {
 
 static int ens_common(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype, int M, int64_t member_stride, int algo,
                       const void* p, const void* t, const uint8_t* mask, double* out, bool map, int lane) {
-  WBX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
+  if (int rc = s1_begin("", ctx, plan)) return rc;
   WBX_REQUIRE(plan->vec == 1, "ensemble kernels use vec=1");
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "WBX_FLAG_MASKED set but mask is NULL");
   WBX_REQUIRE(M >= 1, "ensemble size must be >= 1 (got %d)", M);
   WBX_REQUIRE(algo == WBX_ENS_SORT || algo == WBX_ENS_PAIRWISE || (algo == WBX_ENS_DIAG_LOADONLY && (M == 50 || M == 51)) ||
                   (algo == WBX_ENS_DIAG_PAIRWISE_LDS && M == 51),
               "unknown ensemble algorithm %d", algo);
-  const bool empty = plan->nkey * plan->ndepth * plan->nx == 0;
-  WBX_REQUIRE(empty || (p != nullptr && t != nullptr), "predictions/targets pointer is NULL");
-  WBX_REQUIRE(out != nullptr || plan->nkey == 0, "output pointer is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
-  a.in[3] = mask;
-  a.out = out;
+  if (int rc = s1_operands({"", "output pointer", "predictions/targets pointer"}, ctx, plan, 2, p, t, mask, out, a)) return rc;
   a.M = M;
   a.mstride = member_stride;
   a.lane = lane;

@@ -100,21 +100,11 @@ extern "C" int wbx_ens2_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype
                                 int64_t target_member_stride, const void* p, const void* t, const uint8_t* mask,
                                 double* partial_out) {
   using namespace wbx;
-  WBX_REQUIRE(ctx != nullptr, "ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
+  if (int rc = s1_begin("", ctx, plan)) return rc;
   WBX_REQUIRE(plan->vec == 1 && plan->x_weights == nullptr, "wbx_ens2_partial uses vec = 1 and no folded weights");
   WBX_REQUIRE(M >= 1 && N >= 1, "ensemble sizes must be >= 1 (got %d, %d)", M, N);
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "WBX_FLAG_MASKED set but mask is NULL");
-  const bool empty = plan->nkey * plan->ndepth * plan->nx == 0;
-  WBX_REQUIRE(empty || (p != nullptr && t != nullptr), "predictions/targets pointer is NULL");
-  WBX_REQUIRE(partial_out != nullptr || plan->nkey == 0, "output pointer is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
-  a.in[3] = mask;
-  a.out = partial_out;
+  if (int rc = s1_operands({"", "output pointer", "predictions/targets pointer"}, ctx, plan, 2, p, t, mask, partial_out, a)) return rc;
   a.M = M;
   a.mstride = member_stride;
   a.lane = N;

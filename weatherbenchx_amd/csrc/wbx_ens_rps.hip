@@ -113,12 +113,6 @@ __device__ __forceinline__ void erps_write(double* o, int64_t nj, uint32_t flags
     o[nj] = (double)nvalid;
 }
 
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-
 // x summed.  grid = nkey * nchunk, block = plan->block_threads; rows are dealt to the waves as in s1_xr_kernel.
 template <typename T, int NT, bool RIGHT>
 __global__ void __launch_bounds__(256) erps_xr_kernel(S1Args a, const double* pthr, const double* tthr, int nthr, int nacc,
@@ -228,34 +222,14 @@ __global__ void __launch_bounds__(256) erps_xk_kernel(S1Args a, const double* pt
   erps_write(a.out + ((key * a.nchunk + chunk) * (int64_t)nacc) * a.nx + x, a.nx, a.flags, denom, sum, ngood, nvalid);
 }
 
-template <typename T, int NT, bool RIGHT>
-static int erps_launch(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const double* pthr, const double* tthr, int nthr, int nacc,
-                       double denom) {
-  if (plan->x_kept) {
-    a.nxtile = (int)((plan->nx + plan->block_threads - 1) / plan->block_threads);
-    const int64_t grid = plan->nkey * a.nxtile * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
-    hipLaunchKernelGGL((erps_xk_kernel<T, NT, RIGHT>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, pthr, tthr,
-                       nthr, nacc, denom);
-  } else {
-    const int64_t grid = plan->nkey * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
-    hipLaunchKernelGGL((erps_xr_kernel<T, NT, RIGHT>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, pthr, tthr,
-                       nthr, nacc, denom);
-  }
-  WBX_HIP(hipGetLastError());
-  return 0;
-}
-
-// the kernels are built for 1, 4, 8 and 16 threshold slots; a launch takes the smallest that holds nthr (the slots beyond nthr
-// repeat threshold 0 and are skipped when the numerator is formed)
+// (the threshold slots beyond nthr repeat threshold 0 and are skipped when the numerator is formed)
 template <typename T, bool RIGHT>
 static int erps_dispatch(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, const double* pthr, const double* tthr, int nthr, int nacc,
                          double denom) {
-  if (nthr <= 1) return erps_launch<T, 1, RIGHT>(ctx, plan, a, pthr, tthr, nthr, nacc, denom);
-  if (nthr <= 4) return erps_launch<T, 4, RIGHT>(ctx, plan, a, pthr, tthr, nthr, nacc, denom);
-  if (nthr <= 8) return erps_launch<T, 8, RIGHT>(ctx, plan, a, pthr, tthr, nthr, nacc, denom);
-  return erps_launch<T, WBX_ERPS_MAX_THRESHOLDS, RIGHT>(ctx, plan, a, pthr, tthr, nthr, nacc, denom);
+  return dispatch_slots(nthr, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    return launch_xk_or_xr(ctx, plan, a, erps_xk_kernel<T, NT, RIGHT>, erps_xr_kernel<T, NT, RIGHT>, pthr, tthr, nthr, nacc, denom);
+  });
 }
 
 }  // namespace wbx
@@ -264,12 +238,11 @@ extern "C" int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dt
                                    const double* p_thresholds, const double* t_thresholds, int right_inclusive, const void* p,
                                    const void* t, const uint8_t* mask, double* partial_out) {
   using namespace wbx;
-  static_assert(WBX_ERPS_MAX_THRESHOLDS == 16, "erps_dispatch's largest instantiation");
   // int32 numerator of a point: K (M - 1) M^2 < 2^31
   static_assert((int64_t)WBX_ERPS_MAX_THRESHOLDS * (WBX_ERPS_MAX_MEMBERS - 1) * WBX_ERPS_MAX_MEMBERS * WBX_ERPS_MAX_MEMBERS < ((int64_t)1 << 31),
                 "a point's numerator must fit an int32");
-  WBX_REQUIRE(ctx != nullptr, "wbx_ens_rps_partial: ctx is NULL");
-  if (int rc = check_plan(plan)) return rc;
+  const S1Names names = {"wbx_ens_rps_partial: ", "partial_out", "p/t"};
+  if (int rc = s1_begin(names.who, ctx, plan)) return rc;
   WBX_REQUIRE(nthr >= 1 && nthr <= WBX_ERPS_MAX_THRESHOLDS, "wbx_ens_rps_partial: 1..%d thresholds per launch (got %d)",
               WBX_ERPS_MAX_THRESHOLDS, nthr);
   WBX_REQUIRE(M >= 1 && M <= WBX_ERPS_MAX_MEMBERS, "wbx_ens_rps_partial: 1..%d members (got %d)", WBX_ERPS_MAX_MEMBERS, M);
@@ -279,28 +252,16 @@ extern "C" int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dt
   const bool fair = plan->flags & WBX_FLAG_FAIR;
   WBX_REQUIRE(!fair || M >= 2, "wbx_ens_rps_partial: the fair score needs at least 2 members (got %d)", M);
   WBX_REQUIRE(plan->plane_rows == 0 && plan->x_weights == nullptr, "wbx_ens_rps_partial: no plane mode, no folded x weights");
-  if (plan->flags & WBX_FLAG_MASKED) WBX_REQUIRE(mask != nullptr, "wbx_ens_rps_partial: WBX_FLAG_MASKED set but mask is NULL");
   // |S| stays exact in fp64: a partial meets at most depth_chunk * nx points of at most nthr (M - 1) M^2 each
   WBX_REQUIRE((double)plan->depth_chunk * (double)(plan->nx > 0 ? plan->nx : 1) * (double)nthr * (double)(M > 1 ? M - 1 : 1) * (double)M *
                       (double)M < 9007199254740992.0,
               "wbx_ens_rps_partial: 2^53 or more per partial (depth_chunk * nx * nthr * (M - 1) * M^2)");
-  if (plan->nkey == 0) return 0;
-  WBX_REQUIRE(partial_out != nullptr, "wbx_ens_rps_partial: partial_out is NULL");
-  WBX_HIP(hipSetDevice(ctx->device));
-  const int nacc = (plan->flags & (WBX_FLAG_SKIPNA | WBX_FLAG_MASKED)) ? 2 : 1;
-  if (plan->ndepth == 0 || plan->nx == 0) {  // empty reduction: the sums are zero
-    const size_t n = (size_t)plan->nkey * plan->nchunk * nacc * (size_t)(plan->x_kept ? plan->nx : 1);
-    if (n) WBX_HIP(hipMemsetAsync(partial_out, 0, n * sizeof(double), ctx->stream));
-    return 0;
-  }
-  WBX_REQUIRE(p != nullptr && t != nullptr, "wbx_ens_rps_partial: p/t is NULL");
-  WBX_REQUIRE(p_thresholds != nullptr && t_thresholds != nullptr, "wbx_ens_rps_partial: a threshold table is NULL");
   S1Args a;
-  fill_args(plan, a);
-  a.in[0] = p;
-  a.in[1] = t;
-  a.in[3] = mask;
-  a.out = partial_out;
+  if (int rc = s1_operands(names, ctx, plan, 2, p, t, mask, partial_out, a)) return rc;
+  const int nacc = (int)partial_lanes(plan->flags, 1);
+  bool done;
+  if (int rc = s1_zero_if_empty(ctx, plan, nacc, partial_out, &done); rc || done) return rc;
+  WBX_REQUIRE(p_thresholds != nullptr && t_thresholds != nullptr, "wbx_ens_rps_partial: a threshold table is NULL");
   a.M = M;
   a.mstride = member_stride;
   const double denom = fair ? (double)M * (double)M * (double)(M - 1) : (double)M * (double)M;

@@ -342,6 +342,103 @@ __global__ void __launch_bounds__(1024, 6) s1_xp_kernel(S1Args a, int R) {  // <
   }
 }
 
+inline int fill_args(const wbx_s1_plan* plan, S1Args& a) {
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < WBX_MAX_INPUTS; ++i) {
+    a.key_off[i] = plan->key_off[i];
+    a.depth_off[i] = plan->depth_off[i];
+    a.xstride[i] = plan->xstride[i];
+  }
+  a.gk = plan->gather_key;
+  a.gd = plan->gather_depth;
+  a.gtab = plan->gather_tab;
+  a.ngd = plan->n_gather_depth > 0 ? plan->n_gather_depth : 1;
+  a.nkey = plan->nkey;
+  a.D = plan->ndepth;
+  a.nx = plan->nx;
+  a.dchunk = plan->depth_chunk;
+  a.nchunk = plan->nchunk;
+  a.flags = plan->flags;
+  a.xw = plan->x_weights;
+  return 0;
+}
+
+inline int check_plan(const wbx_s1_plan* p) {
+  WBX_REQUIRE(p != nullptr, "plan is NULL");
+  WBX_REQUIRE(p->nkey >= 0 && p->ndepth >= 0 && p->nx >= 0, "negative plan extent");
+  WBX_REQUIRE(p->nchunk >= 1 && p->depth_chunk >= 1, "nchunk/depth_chunk must be >= 1");
+  WBX_REQUIRE((int64_t)p->nchunk * p->depth_chunk >= p->ndepth, "chunks do not cover depth");
+  WBX_REQUIRE(p->block_threads == 64 || p->block_threads == 128 || p->block_threads == 256,
+              "block_threads must be 64, 128 or 256 (got %d)", p->block_threads);
+  WBX_REQUIRE(p->vec == 1 || p->vec == 4, "vec must be 1 or 4 (got %d)", p->vec);
+  if (p->vec == 4) {
+    WBX_REQUIRE(p->x_kept || p->nx % 4 == 0, "vec=4 with x summed needs nx %% 4 == 0");
+    for (int i = 0; i < WBX_MAX_INPUTS; ++i)
+      WBX_REQUIRE(p->xstride[i] == 0 || p->xstride[i] == 1, "vec=4 needs unit/zero x strides");
+  }
+  return 0;
+}
+
+// The helpers below are `static`: libwbx_hip.so exports every other symbol, and its symbol list is part of what a build is
+// compared by.
+// What an entry calls itself and its pointers in its messages (callers and tests match on these texts).
+struct S1Names {
+  const char* who;  // "" or "wbx_..._partial: "
+  const char* out;
+  const char* in;
+};
+
+// The preamble of every stage-1 entry, in two stages around the family's own requirements (which read the plan).
+static inline int s1_begin(const char* who, wbx_ctx* ctx, const wbx_s1_plan* plan) {
+  WBX_REQUIRE(ctx != nullptr, "%sctx is NULL", who);
+  return check_plan(plan);
+}
+
+// Stage two: the mask under WBX_FLAG_MASKED (`mask_if_empty` = false: unless the extent is empty, as the categorical entries have
+// always had it), the output unless there is no key, the first `nin` of p / t unless the extent is empty; then the context's
+// device and the launch arguments.
+static inline int s1_operands(const S1Names& n, wbx_ctx* ctx, const wbx_s1_plan* plan, int nin, const void* p, const void* t,
+                              const uint8_t* mask, double* out, S1Args& a, bool mask_if_empty = true) {
+  const bool empty = plan->nkey == 0 || plan->ndepth == 0 || plan->nx == 0;
+  if ((plan->flags & WBX_FLAG_MASKED) && (mask_if_empty || !empty))
+    WBX_REQUIRE(mask != nullptr, "%sWBX_FLAG_MASKED set but mask is NULL", n.who);
+  WBX_REQUIRE(out != nullptr || plan->nkey == 0, "%s%s is NULL", n.who, n.out);
+  WBX_REQUIRE(empty || (p != nullptr && (t != nullptr || nin < 2)), "%s%s is NULL", n.who, n.in);
+  WBX_HIP(hipSetDevice(ctx->device));
+  fill_args(plan, a);
+  a.in[0] = p;
+  a.in[1] = t;
+  a.in[3] = mask;
+  a.out = out;
+  return 0;
+}
+
+// Lanes of a partial: `nl` value lanes, one count lane more under a mask, one per value lane under skipna.
+static inline int64_t partial_lanes(uint32_t flags, int64_t nl) {
+  return (flags & WBX_FLAG_SKIPNA) ? 2 * nl : ((flags & WBX_FLAG_MASKED) ? nl + 1 : nl);
+}
+
+// An empty reduction: the sums are zero and nothing is launched (`*done`).
+static inline int s1_zero_if_empty(wbx_ctx* ctx, const wbx_s1_plan* plan, int nacc, double* out, bool* done) {
+  *done = plan->nkey == 0 || plan->ndepth == 0 || plan->nx == 0;
+  if (!*done) return 0;
+  const size_t n = (size_t)plan->nkey * plan->nchunk * nacc * (size_t)(plan->x_kept ? plan->nx : 1);
+  if (n) WBX_HIP(hipMemsetAsync(out, 0, n * sizeof(double), ctx->stream));
+  return 0;
+}
+
+// Blocks of a partial launch: one per key and depth chunk, times the x tiles of `x_per_block` positions (a.nxtile) where that is
+// not 0.
+static inline int s1_grid(const wbx_s1_plan* plan, int64_t x_per_block, S1Args& a, int64_t* grid) {
+  *grid = plan->nkey * plan->nchunk;
+  if (x_per_block > 0) {
+    a.nxtile = (int)((plan->nx + x_per_block - 1) / x_per_block);
+    *grid *= a.nxtile;
+  }
+  WBX_REQUIRE(*grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)*grid);
+  return 0;
+}
+
 template <class Op>
 int launch_plane(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a) {
   const int R = plan->plane_rows;
@@ -572,63 +669,16 @@ __global__ void __launch_bounds__(256) s1_map_kernel(S1Args a) {
   a.out[(key * a.D + d) * a.nx + x] = r;
 }
 
-inline int fill_args(const wbx_s1_plan* plan, S1Args& a) {
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < WBX_MAX_INPUTS; ++i) {
-    a.key_off[i] = plan->key_off[i];
-    a.depth_off[i] = plan->depth_off[i];
-    a.xstride[i] = plan->xstride[i];
-  }
-  a.gk = plan->gather_key;
-  a.gd = plan->gather_depth;
-  a.gtab = plan->gather_tab;
-  a.ngd = plan->n_gather_depth > 0 ? plan->n_gather_depth : 1;
-  a.nkey = plan->nkey;
-  a.D = plan->ndepth;
-  a.nx = plan->nx;
-  a.dchunk = plan->depth_chunk;
-  a.nchunk = plan->nchunk;
-  a.flags = plan->flags;
-  a.xw = plan->x_weights;
-  return 0;
-}
-
-inline int check_plan(const wbx_s1_plan* p) {
-  WBX_REQUIRE(p != nullptr, "plan is NULL");
-  WBX_REQUIRE(p->nkey >= 0 && p->ndepth >= 0 && p->nx >= 0, "negative plan extent");
-  WBX_REQUIRE(p->nchunk >= 1 && p->depth_chunk >= 1, "nchunk/depth_chunk must be >= 1");
-  WBX_REQUIRE((int64_t)p->nchunk * p->depth_chunk >= p->ndepth, "chunks do not cover depth");
-  WBX_REQUIRE(p->block_threads == 64 || p->block_threads == 128 || p->block_threads == 256,
-              "block_threads must be 64, 128 or 256 (got %d)", p->block_threads);
-  WBX_REQUIRE(p->vec == 1 || p->vec == 4, "vec must be 1 or 4 (got %d)", p->vec);
-  if (p->vec == 4) {
-    WBX_REQUIRE(p->x_kept || p->nx % 4 == 0, "vec=4 with x summed needs nx %% 4 == 0");
-    for (int i = 0; i < WBX_MAX_INPUTS; ++i)
-      WBX_REQUIRE(p->xstride[i] == 0 || p->xstride[i] == 1, "vec=4 needs unit/zero x strides");
-  }
-  return 0;
-}
-
 // Launch helpers -----------------------------------------------------------------------------
 template <class Op, int V>
 int launch_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, bool mask_row_in_lds = false) {
-  if (plan->nkey == 0) return 0;
-  const int64_t nj = plan->x_kept ? plan->nx : 1;
-  if (plan->ndepth == 0 || plan->nx == 0) {
-    // empty reduction: sums are zero
-    size_t n = (size_t)plan->nkey * plan->nchunk * Op::NACC * (size_t)nj;
-    if (n) WBX_HIP(hipMemsetAsync(a.out, 0, n * sizeof(double), ctx->stream));
-    return 0;
-  }
+  bool done;
+  if (int rc = s1_zero_if_empty(ctx, plan, Op::NACC, a.out, &done); rc || done) return rc;
+  int64_t grid;
+  if (int rc = s1_grid(plan, plan->x_kept ? (int64_t)plan->block_threads * V : 0, a, &grid)) return rc;
   if (plan->x_kept) {
-    const int64_t per_block = (int64_t)plan->block_threads * V;
-    a.nxtile = (int)((plan->nx + per_block - 1) / per_block);
-    const int64_t grid = plan->nkey * a.nxtile * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
     hipLaunchKernelGGL((s1_xk_kernel<Op, V>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a);
   } else {
-    const int64_t grid = plan->nkey * plan->nchunk;
-    WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
     if constexpr (op_has_mrow<Op>::value) {
       if (mask_row_in_lds) {
         hipLaunchKernelGGL((s1_xr_kernel<Op, V, true>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a);
@@ -651,6 +701,27 @@ int launch_map(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a) {
   hipLaunchKernelGGL((s1_map_kernel<Op>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a);
   WBX_HIP(hipGetLastError());
   return 0;
+}
+
+// The two integer-count families (wbx_contingency.hip, wbx_ens_rps.hip): x kept runs `xk` with one x per lane, x summed `xr`.
+template <class... Params, class... Args>
+static int launch_xk_or_xr(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, void (*xk)(S1Args, Params...),
+                           void (*xr)(S1Args, Params...), Args... args) {
+  int64_t grid;
+  if (int rc = s1_grid(plan, plan->x_kept ? plan->block_threads : 0, a, &grid)) return rc;
+  hipLaunchKernelGGL(plan->x_kept ? xk : xr, dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a, args...);
+  WBX_HIP(hipGetLastError());
+  return 0;
+}
+
+// Their kernels are built for 1, 4, 8 and 16 threshold slots; a launch takes the smallest that holds nthr: f(integral_constant<NT>).
+static_assert(WBX_CONT_MAX_THRESHOLDS == 16 && WBX_ERPS_MAX_THRESHOLDS == 16, "dispatch_slots' largest instantiation");
+template <class F>
+static int dispatch_slots(int nthr, F f) {
+  if (nthr <= 1) return f(std::integral_constant<int, 1>{});
+  if (nthr <= 4) return f(std::integral_constant<int, 4>{});
+  if (nthr <= 8) return f(std::integral_constant<int, 8>{});
+  return f(std::integral_constant<int, 16>{});
 }
 
 }  // namespace wbx

@@ -8,6 +8,7 @@ tensors already resident in HBM (consumed in place through their strides: no cop
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import dataclasses
@@ -723,6 +724,73 @@ def _try_det_spectra(ctx, inputs, dplan, plan, devs, dtype_code, func, make_out,
   return _FoldedS2((det_out.ptr, det_shape)) if folded else out
 
 
+# ---- the stage-1 families ------------------------------------------------------------------------------------------------------
+# What a launch takes beyond its inputs, in the positions `_run_s1`'s callers have always used (a plain tuple still does).
+EnsArgs = collections.namedtuple('EnsArgs', 'm mstride algo')
+RpsEnsArgs = collections.namedtuple('RpsEnsArgs', 'm mstride')
+Ens2Args = collections.namedtuple('Ens2Args', 'm mstride n_t tstride')
+CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  # thr: a table; None with cstride: a field (input 2)
+ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
+RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
+_table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
+
+
+def _cat_operands(ctx, devs, func, ens, cat, mdim):
+  field = cat.get('thr_field') is not None
+  thr = _threshold_table(ctx, cat['thresholds']) if cat.get('thresholds') is not None and not field else None
+  return int(cat['ncat']), None, CatArgs(cat['func'], int(cat['ncat']), cat.get('M', 1) if mdim else 1,
+                                         devs[0].layout.stride(mdim) if mdim else 0, thr,
+                                         devs[2].layout.stride(cat['cat_dim']) if field else None)
+
+
+def _cont_operands(ctx, devs, func, ens, cat, mdim):
+  nthr = int(np.asarray(cat['thresholds']).size)
+  if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
+    raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
+  return _hip.CONT_CELLS * nthr, None, ContArgs(nthr, _threshold_table(ctx, cat['thresholds']))
+
+
+def _erps_operands(ctx, devs, func, ens, cat, mdim):
+  nthr = int(np.asarray(cat['p_thresholds']).size)
+  if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS or int(np.asarray(cat['t_thresholds']).size) != nthr:
+    raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} prediction and as many target thresholds '
+                     f"(got {nthr} and {int(np.asarray(cat['t_thresholds']).size)})")
+  if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
+    raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
+  return 1, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), RpsArgs(
+      nthr, _threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
+
+
+# kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
+#           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
+#         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
+#           the `ens` tuple goes in as it stands (its fields are the entry's integers, in the entry's order)
+_Kind = collections.namedtuple('_Kind', 'operands keep call')
+_KINDS = {
+    'det': _Kind(lambda ctx, devs, func, ens, cat, mdim: (_hip.DET_LANES[func], None, None), (),
+                 lambda d, out, dt, func, ens, cat: ('wbx_det_partial', (func, dt, d[0], d[1], d[2], d[3], out))),
+    'ens': _Kind(lambda ctx, devs, func, ens, cat, mdim:
+                 (_hip.ENS_LANES, EnsArgs(ens['M'], devs[0].layout.stride(mdim), ens['algo']), None), (),
+                 lambda d, out, dt, func, ens, cat: ('wbx_ens_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
+    'ens2': _Kind(lambda ctx, devs, func, ens, cat, mdim:
+                  (_hip.ENS2_LANES, Ens2Args(ens['M'], devs[0].layout.stride(mdim), ens['N'], devs[1].layout.stride(mdim)), None), (),
+                  lambda d, out, dt, func, ens, cat: ('wbx_ens2_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
+    'cat': _Kind(_cat_operands, ('thr',),
+                 lambda d, out, dt, func, ens, cat:  # a threshold field depends on the statistic's dims: input 2 of the plan
+                 ('wbx_cat_exceed_field', (dt, int(cat.ncat), int(cat.m), int(cat.mstride), d[0], d[1], d[2], int(cat.cstride), d[3], out))
+                 if cat.cstride is not None else
+                 ('wbx_cat_partial', (int(cat.func), dt, int(cat.ncat), int(cat.m), int(cat.mstride), d[0], d[1], _table_ptr(cat.thr),
+                                      d[3], out))),
+    'cont': _Kind(_cont_operands, ('thr',),
+                  lambda d, out, dt, func, ens, cat:
+                  ('wbx_contingency_partial', (dt, int(cat.nthr), d[0], d[1], _table_ptr(cat.thr), d[3], out))),
+    'erps': _Kind(_erps_operands, ('p_thr', 't_thr'),
+                  lambda d, out, dt, func, ens, cat:
+                  ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
+                                           int(bool(cat.right)), d[0], d[1], d[3], out))),
+}
+
+
 def _run_s1(ctx, kind: str, dplan: _PlanOnDevice, plan: planner.S1Plan, devs: Sequence[_Dev | None], dtype_code: int,
             nlanes_total: int, func: int = 0, ens=None, cat=None, inputs=None, fold=None):
   """-> the stage-1 partial's device buffer, or a `_FoldedS2` when the launch has done stage 2 as well (`fold`: see
@@ -733,47 +801,16 @@ def _run_s1(ctx, kind: str, dplan: _PlanOnDevice, plan: planner.S1Plan, devs: Se
     if hit is not False:
       return hit  # the partial's buffer, or a _FoldedS2
   out = _scratch(ctx, 'partial', n * 8)
-  ptr = lambda d: C.c_void_p(d.ptr) if d is not None else None
 
-  def call():  # idempotent: a repetition overwrites the same partial buffer
-    if kind == 'det':
-      _hip.check(ctx.lib.wbx_det_partial(ctx.handle, C.byref(dplan.struct), func, dtype_code, ptr(devs[0]),
-                                         ptr(devs[1]), ptr(devs[2]), ptr(devs[3]), C.c_void_p(out.ptr)), 'wbx_det_partial')
-    elif kind == 'cat' and cat[5] is not None:  # thresholds that depend on the statistic's dims: input 2 of the plan
-      cfunc, ncat, m, mstride, _, cstride = cat
-      _hip.check(ctx.lib.wbx_cat_exceed_field(ctx.handle, C.byref(dplan.struct), dtype_code, int(ncat), int(m), int(mstride),
-                                              ptr(devs[0]), ptr(devs[1]), ptr(devs[2]), int(cstride), ptr(devs[3]),
-                                              C.c_void_p(out.ptr)), 'wbx_cat_exceed_field')
-    elif kind == 'ens2':
-      m, mstride, n_t, tstride = ens
-      _hip.check(ctx.lib.wbx_ens2_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(m), int(mstride), int(n_t), int(tstride),
-                                          ptr(devs[0]), ptr(devs[1]), ptr(devs[3]), C.c_void_p(out.ptr)), 'wbx_ens2_partial')
-    elif kind == 'cont':
-      nthr, thr = cat
-      _hip.check(ctx.lib.wbx_contingency_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(nthr), ptr(devs[0]),
-                                                 ptr(devs[1]), ptr(thr), ptr(devs[3]), C.c_void_p(out.ptr)),
-                 'wbx_contingency_partial')
-    elif kind == 'erps':
-      m, mstride = ens
-      nthr, p_thr, t_thr, right = cat
-      _hip.check(ctx.lib.wbx_ens_rps_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(m), int(mstride), int(nthr),
-                                             ptr(p_thr), ptr(t_thr), int(bool(right)), ptr(devs[0]), ptr(devs[1]), ptr(devs[3]),
-                                             C.c_void_p(out.ptr)), 'wbx_ens_rps_partial')
-    elif kind == 'cat':
-      cfunc, ncat, m, mstride, thr, _ = cat
-      _hip.check(ctx.lib.wbx_cat_partial(ctx.handle, C.byref(dplan.struct), int(cfunc), dtype_code, int(ncat), int(m),
-                                         int(mstride), ptr(devs[0]), ptr(devs[1]), ptr(thr), ptr(devs[3]),
-                                         C.c_void_p(out.ptr)), 'wbx_cat_partial')
-    else:
-      m, mstride, algo = ens
-      _hip.check(ctx.lib.wbx_ens_partial(ctx.handle, C.byref(dplan.struct), dtype_code, int(m), int(mstride),
-                                         int(algo), ptr(devs[0]), ptr(devs[1]), ptr(devs[3]), C.c_void_p(out.ptr)), 'wbx_ens_partial')
+  def call():  # idempotent: a repetition overwrites the same partial buffer (the arguments are built in here, as they always were)
+    name, args = _KINDS[kind].call([_table_ptr(d) for d in devs], C.c_void_p(out.ptr), dtype_code, func, ens, cat)
+    _hip.check(getattr(ctx.lib, name)(ctx.handle, C.byref(dplan.struct), *args), name)
   if S1_EVENT_LOG is None:
     call()
   else:
     timed_launch(ctx, call, kind=kind, vec=plan.vec, x_kept=plan.x_kept, plane_rows=plan.plane_rows,
                  x_weighted=plan.x_weights is not None, flat=plan.x_weights is not None and plan.plane_rows > 0,
-                 grid=plan.nkey * plan.nchunk, block=plan.block_threads, algo=int(ens[2]) if kind == 'ens' else None,
+                 grid=plan.nkey * plan.nchunk, block=plan.block_threads, algo=int(EnsArgs(*ens).algo) if kind == 'ens' else None,
                  flags=int(plan.flags))
   return out
 
@@ -1520,51 +1557,16 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
       else:
         hit = None
   plan, dplan = hit if hit is not None else _planned(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, flags)
-  nl = _hip.DET_LANES[func] if kind == 'det' else (int(cat['ncat']) if kind == 'cat' else
-                                                   (_hip.ENS2_LANES if kind == 'ens2' else _hip.ENS_LANES))
-  if kind == 'cont':
-    nthr = int(np.asarray(cat['thresholds']).size)
-    if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
-      raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
-    nl = _hip.CONT_CELLS * nthr
-  if kind == 'erps':
-    nthr = int(np.asarray(cat['p_thresholds']).size)
-    if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS or int(np.asarray(cat['t_thresholds']).size) != nthr:
-      raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} prediction and as many target thresholds '
-                       f"(got {nthr} and {int(np.asarray(cat['t_thresholds']).size)})")
-    if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
-      raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
-    nl = 1
+  nl, ens_args, cat_args = _KINDS[kind].operands(ctx, devs, func, ens, cat, member_dim)
   counted = bool(flags & 3)
   shared_count = counted and not (flags & _hip.FLAG_SKIPNA)  # mask only: one count lane for every statistic
   nl_total = nl + 1 if shared_count else nl * (2 if counted else 1)
-  ens_args = cat_args = None
-  if kind == 'ens':
-    ens_args = (ens['M'], devs[0].layout.stride(member_dim), ens['algo'])
-  if kind == 'ens2':
-    ens_args = (ens['M'], devs[0].layout.stride(member_dim), ens['N'], devs[1].layout.stride(member_dim))
-  if kind == 'cat':
-    thr = None
-    if cat.get('thresholds') is not None and thr_field is None:
-      thr = _threshold_table(ctx, cat['thresholds'])
-    cat_args = (cat['func'], nl, cat.get('M', 1) if member_dim else 1,
-                devs[0].layout.stride(member_dim) if member_dim else 0, thr,
-                None if thr_field is None else devs[2].layout.stride(cat['cat_dim']))
-  cont_thr = None
-  if kind == 'cont':
-    cont_thr = _threshold_table(ctx, cat['thresholds'])
-    cat_args = (nthr, cont_thr)
-  erps_thr = (None, None)
-  if kind == 'erps':
-    erps_thr = (_threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']))
-    ens_args = (ens['M'], devs[0].layout.stride(member_dim))
-    cat_args = (nthr, erps_thr[0], erps_thr[1], bool(cat['right_inclusive']))
   w_buf = _device_w(ctx, plan, w_da, bin_dims)
   # (a chunk that is being recorded: the record keeps what the launches below point at -- plan tables, weights / bins / atom
   #  tables, inputs that do not follow the chunk such as the climatology, threshold tables)
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
-  replay.keep(dplan, w_buf, cont_thr if kind == 'cont' else (cat_args[4] if cat_args and kind == 'cat' else None), *erps_thr,
+  replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in _KINDS[kind].keep),
               devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None)
   bin_shape = w_buf.bin_shape
   s2 = planner.build_s2_plan(plan, nl_total, w_buf.shape[-1])

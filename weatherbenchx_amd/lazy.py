@@ -170,6 +170,25 @@ class ClimatologyRef(xr.LazyPickleMixin, xr.DataArray):
     return xr.DataArray(g, dims=self.aligned_dims(), coords=coords, _raw_coords=True)
 
 
+def _reduce_in_blocks(subs, reduce_one, join):
+  """reduce_one(sub) -> (values, counts, out_dims) for every block of `subs`, one launch each, joined on the host right away."""
+  values, counts, out_dims = [], [], None
+  with engine.synchronous_results():
+    for sub in subs:
+      v, c, out_dims = reduce_one(sub)
+      values.append(np.array(v, dtype=np.float64))  # (own memory: the next launch reuses the result buffers)
+      counts.append(np.array(c, dtype=np.float64))
+  return join(values), join(counts), out_dims
+
+
+def _group_known(p, t, kind: str, pred=lambda key: True) -> bool:
+  """A group of kind `kind` of these very objects exists (`pred`: of the rest of its key): an earlier statistic has checked
+  their frames."""
+  table = p.__dict__.get('_wbx_groups')
+  return bool(table) and any(k[0] == kind and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and pred(k)
+                             and v[0]() is t and v[1]() is not None for k, v in table.items())
+
+
 class FusedGroup:
   """All fused statistics over one (predictions, targets[, climatology]) triple."""
 
@@ -217,23 +236,19 @@ class FusedGroup:
   def reduce(self, reduce_dims, w_da, bin_dims, *, use_mask: bool, skipna: bool, ens_params=None, extra_reduce=()):
     inputs, func = self.inputs_and_func()
     mask = self.mask if use_mask else None
-    ens = None
-    if self.kind == 'ens':
-      ens = dict(self.ens, **(ens_params or {}))
-    if self.kind == 'ens2':
-      return engine.reduce_statistics('ens2', inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce),
-                                      w_da, bin_dims, mask=mask, skipna=skipna, ens=self.ens)
+    reduce_dims = tuple(reduce_dims) + tuple(extra_reduce)
+    if self.kind in ('det', 'ens'):
+      ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
+      return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
+                                 skipna=skipna, clim=self.clim, ens=ens)
+    # 'ens2', 'erps': one launch (the fair / inclusive settings of an 'erps' group are its own); 'cat', 'cont': one per block
+    launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                                  skipna=skipna, ens=self.ens, cat=cat)
     if self.kind == 'cat':
-      return self._reduce_cat(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
-    if self.kind == 'cont':
-      return self._reduce_cont(inputs, tuple(reduce_dims) + tuple(extra_reduce), w_da, bin_dims, mask, skipna)
-    if self.kind == 'erps':  # one value lane, one launch (wbx_ens_rps_partial): fair / inclusive are the group's own
-      return engine.reduce_statistics('erps', inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
-                                      bin_dims, mask=mask, skipna=skipna, ens=self.ens, cat=self.cat)
-    return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, tuple(reduce_dims) + tuple(extra_reduce), w_da,
-                               bin_dims, func=func, mask=mask, skipna=skipna, clim=self.clim, ens=ens)
+      return self._reduce_cat(launch, mask, skipna)
+    return self._reduce_cont(launch) if self.kind == 'cont' else launch(self.cat)
 
-  def _reduce_cat(self, inputs, reduce_dims, w_da, bin_dims, mask, skipna):
+  def _reduce_cat(self, launch, mask, skipna):
     """Indicator statistics: one launch where the categories fit its LDS columns (cat_lanes_per_launch), else -- thresholds
     are independent of one another -- one launch per block of categories that fits, the results joined along the category
     axis.  The ranks of a histogram are not independent (a point adds to ONE of its M + 1 bins, whichever): no split."""
@@ -245,37 +260,22 @@ class FusedGroup:
       raise ValueError(f'RankHistogram: {ncat - 1} members need {ncat} rank lanes, but one launch holds {block} {how} '
                        f'(at most {block - 1} members); the ranks of a histogram cannot be split over launches')
     if ncat <= block:
-      return engine.reduce_statistics('cat', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
-                                      skipna=skipna, cat=cat)
-    values, counts, out_dims = [], [], None
-    with engine.synchronous_results():  # the blocks are joined on the host right away
-      for sub in self._cat_blocks(block):
-        v, c, out_dims = engine.reduce_statistics('cat', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
-                                                  skipna=skipna, cat=sub)
-        values.append(np.array(v, dtype=np.float64))  # (own memory: the next launch reuses the result buffers)
-        counts.append(np.array(c, dtype=np.float64))
-    return np.concatenate(values, axis=0), np.concatenate(counts, axis=0), out_dims
+      return launch(cat)
+    return _reduce_in_blocks(self._cat_blocks(block), launch, lambda parts: np.concatenate(parts, axis=0))
 
-  def _reduce_cont(self, inputs, reduce_dims, w_da, bin_dims, mask, skipna):
+  def _reduce_cont(self, launch):
     """Thresholded contingency tables: one launch for up to _hip.CONT_MAX_THRESHOLDS thresholds; more are cut into blocks --
     thresholds are independent of one another --, one launch each, joined on the host cell by cell: the result is
     (4 * K,) + out_dims with lane cell * K + k whatever the number of launches."""
     thr = np.asarray(self.cat['thresholds'], np.float64)
     nthr, block = int(thr.size), _hip.CONT_MAX_THRESHOLDS
     if nthr <= block:
-      return engine.reduce_statistics('cont', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
-                                      skipna=skipna, cat={'thresholds': thr})
-    values, counts, out_dims = [], [], None
-    with engine.synchronous_results():  # the blocks are joined on the host right away
-      for k0 in range(0, nthr, block):
-        sub = np.ascontiguousarray(thr[k0:k0 + block])
-        v, c, out_dims = engine.reduce_statistics('cont', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
-                                                  skipna=skipna, cat={'thresholds': sub})
-        # (own memory: the next launch reuses the result buffers) -- (cell, k of the block) + out_dims
-        values.append(np.array(v, dtype=np.float64).reshape((_hip.CONT_CELLS, sub.size) + v.shape[1:]))
-        counts.append(np.array(c, dtype=np.float64).reshape((_hip.CONT_CELLS, sub.size) + c.shape[1:]))
-    join = lambda parts: np.concatenate(parts, axis=1).reshape((_hip.CONT_CELLS * nthr,) + parts[0].shape[2:])
-    return join(values), join(counts), out_dims
+      return launch({'thresholds': thr})
+    # (cell, k of the block) + out_dims; the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from
+    cells = lambda a: a.reshape((_hip.CONT_CELLS, a.shape[0] // _hip.CONT_CELLS) + a.shape[1:])
+    return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block])} for k0 in range(0, nthr, block)], launch,
+                             lambda parts: np.concatenate([cells(a) for a in parts], axis=1).reshape(
+                                 (_hip.CONT_CELLS * nthr,) + parts[0].shape[1:]))
 
   def _cat_blocks(self, block: int):
     """self.cat cut into runs of at most `block` categories (kept: a block's threshold table / field is uploaded once)."""
@@ -500,10 +500,8 @@ def det_statistic(stat_name: str, p, t, climatology_ref: ClimatologyRef | None =
   p, t = xr.as_dataarray(p), xr.as_dataarray(t)
   if isinstance(p, LazyEnsembleMean) and p.is_lazy and stat_name == 'SquaredError':
     return ens_statistic('EnsembleMeanSquaredError', p._source, t, p._ensemble_dim)  # pylint: disable=protected-access
-  table = p.__dict__.get('_wbx_groups')
-  if not (table and any(k[0] == 'det' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and v[0]() is t
-                        and v[1]() is not None for k, v in table.items())):
-    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier statistic has checked their frames)
+  if not _group_known(p, t, 'det'):
+    p, t = _aligned(p, t)
   # one group per (p, t): Error/AbsoluteError/SquaredError and the anomaly statistics of the FIRST
   # climatology share a launch; a second, different climatology gets its own group.
   grp = _group_for('det', p, t)
@@ -543,10 +541,8 @@ def ens_statistic(stat_name: str, p, t, ensemble_dim: str, *, use_sort=False, fa
     if not (set(t.dims) <= set(p.dims) and _same_mask(p, t)):
       t = first_member(p, ensemble_dim)  # a companion with exactly the predictions' frame
     coord_names = frozenset(p._coords)  # pylint: disable=protected-access
-  table = p.__dict__.get('_wbx_groups')
-  if not (table and any(k[0] == 'ens' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and k[3] == ensemble_dim
-                        and v[0]() is t and v[1]() is not None for k, v in table.items())):
-    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier statistic has checked their frames)
+  if not _group_known(p, t, 'ens', lambda k: k[3] == ensemble_dim):
+    p, t = _aligned(p, t)
   m = p.sizes[ensemble_dim]
   grp = _group_for('ens', p, t, ens={'member_dim': ensemble_dim, 'M': m})
   # use_sort=False (the reference's default, probabilistic.py:644) asks for the O(M^2) pair form of the SAME number -- the
@@ -692,11 +688,9 @@ def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr
     raise ValueError(f'{threshold_dim!r} is already a dimension of the inputs')
   values = list(thresholds)
   thr = np.asarray(values, np.float64).reshape(-1)
-  table = p.__dict__.get('_wbx_groups')
   ckey = ('cont', threshold_dim, thr.tobytes())
-  if not (table and any(k[0] == 'cont' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and k[4] == ckey
-                        and v[0]() is t and v[1]() is not None for k, v in table.items())):
-    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier cell has checked their frames)
+  if not _group_known(p, t, 'cont', lambda k: k[4] == ckey):
+    p, t = _aligned(p, t)
   cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim}
   grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
   return LazyContingency(grp, cell, threshold_dim, name=p.name)
@@ -717,10 +711,8 @@ def ens_rps_statistic(p, t, ensemble_dim: str, p_thr, t_thr, fair: bool, right_i
   if pa.size != tb.size:
     raise ValueError(f'{pa.size} prediction thresholds against {tb.size} target thresholds')
   ckey = ('erps', pa.tobytes(), tb.tobytes(), bool(fair), bool(right_inclusive), bin_dim)
-  table = p.__dict__.get('_wbx_groups')
-  if not (table and any(k[0] == 'erps' and k[1] == id(t) and k[2] == t.__dict__.get('_mutations', 0) and k[3] == ensemble_dim
-                        and v[0]() is t and v[1]() is not None for k, v in table.items())):
-    p, t = _aligned(p, t)  # (a group of these very objects exists: an earlier statistic has checked their frames)
+  if not _group_known(p, t, 'erps', lambda k: k[3] == ensemble_dim):
+    p, t = _aligned(p, t)
   ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': bool(fair)}
   cat = {'p_thresholds': pa, 't_thresholds': tb, 'right_inclusive': bool(right_inclusive), 'p_values': p_values,
          't_values': t_values, 'bin_dim': bin_dim}
