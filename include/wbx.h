@@ -402,6 +402,33 @@ int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_
                         int nthr, const double* p_thresholds, const double* t_thresholds /* DEVICE float64[nthr] each */,
                         int right_inclusive, const void* p, const void* t, const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: energy score of an ensemble, both terms (joined ABI 13) -------------------------------------------
+ * EnergyScoreSkill and EnergyScoreSpread (probabilistic.py:480-551) of an ensemble of predictions against a target, in one pass
+ * over p and t instead of one whole-array pass per cyclic member offset.  p has a member axis of length M and element stride
+ * `member_stride`, and p and t have a norm run of L elements with element strides `p_norm_stride` / `t_norm_stride` (the norm dims
+ * of the score, collapsed to one run); neither is part of key / depth / x.  Per point, with members x_m in R^L and target y in R^L:
+ *     lane 0 (skill)  = (sum_m ||x_m - y||) / M
+ *     lane 1 (spread) = (sum_{m != m'} ||x_m - x_m'||) / D,   D = M (M - 1) under WBX_FLAG_FAIR, M^2 otherwise
+ * Differences, their squares and the sum of squares are formed in the input type (fma, in the order of the run), the square root
+ * is correctly rounded in the input type, everything after that is float64.  The squared distance is never formed from
+ * ||a||^2 + ||b||^2 - 2 a.b.  NaN and inf are what IEEE arithmetic makes of them: a NaN member makes both lanes NaN, a NaN target
+ * lane 0 only; an infinite member against finite ones gives +inf; two infinite members of one sign make lane 1 NaN (inf - inf)
+ * and leave lane 0 +inf; a member is never paired with itself.
+ * TWO value lanes (WBX_ENRG_LANES).  Count lanes follow the library's convention (none / one shared / one per value lane), and
+ * NaN-ness is per lane: without flags a NaN lane of a point poisons that lane of its partial; under WBX_FLAG_MASKED alone a point
+ * contributes exactly 0 where the mask is 0 and poisons (per lane) where it is not; under WBX_FLAG_SKIPNA a NaN lane of a point is
+ * counted out of that lane.  partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial: wbx_s1_partial_len with lanes = 2,
+ * wbx_contract and wbx_contract_bits serve it unchanged.  The result is a function of the inputs and the plan only, bit for bit:
+ * every sum is formed in a fixed order, nothing is added atomically.
+ * Refused (WBX_ERR_INVALID, output untouched): M outside 2..WBX_ENRG_MAX_MEMBERS, L < 1, an unknown dtype, flags beyond
+ * MASKED | SKIPNA | FAIR, WBX_FLAG_MASKED with a NULL mask, plane_rows != 0 or x_weights.  vec = 4 is accepted and ignored.
+ * nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_ENRG_LANES 2
+#define WBX_ENRG_MAX_MEMBERS 64 /* M + 1 vectors padded to 4: 17 x 17 blocks of 4 x 4 pairs, 153 of them per point */
+int wbx_ens_energy_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                           int64_t L, int64_t p_norm_stride, int64_t t_norm_stride, const void* p, const void* t,
+                           const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -621,7 +648,7 @@ typedef enum wbx_fn {
   WBX_FN_CONTRACT = 6, WBX_FN_CONTRACT_BITS = 7, WBX_FN_DET_BINNED = 8, WBX_FN_ENS_BINNED = 9, WBX_FN_ZONAL_SPECTRUM = 10,
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
-  WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21
+  WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -455,6 +455,16 @@ def ens_rps_available(ctx) -> bool:
     return False
 
 
+def ens_energy_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_energy_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_energy_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -732,6 +742,7 @@ Ens2Args = collections.namedtuple('Ens2Args', 'm mstride n_t tstride')
 CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  # thr: a table; None with cstride: a field (input 2)
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
+EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -761,6 +772,30 @@ def _erps_operands(ctx, devs, func, ens, cat, mdim):
       nthr, _threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
 
 
+def norm_run(layout, dims, sizes):
+  """The norm dims `dims` of an input with this layout as ONE run -> (length, element stride), or None where they do not collapse
+  to one (dims of size 1 do not matter; a run of one element has stride 0)."""
+  live = sorted(((abs(layout.stride(d)), layout.stride(d), int(sizes[d])) for d in dims if int(sizes[d]) != 1), key=lambda v: v[0])
+  length = int(np.prod([int(sizes[d]) for d in dims], dtype=np.int64))
+  if not live:
+    return length, 0
+  if live[0][1] <= 0:
+    return None
+  for (_, s0, n0), (_, s1, _) in zip(live, live[1:]):
+    if s1 != s0 * n0:
+      return None
+  return length, live[0][1]
+
+
+def _enrg_operands(ctx, devs, func, ens, cat, mdim):
+  if not 2 <= int(ens['M']) <= _hip.ENRG_MAX_MEMBERS:
+    raise ValueError(f"one energy score launch takes 2..{_hip.ENRG_MAX_MEMBERS} members (got {ens['M']})")
+  runs = [norm_run(devs[i].layout, ens['norm_dims'], ens['norm_sizes']) for i in (0, 1)]
+  if runs[0] is None or runs[1] is None:
+    raise ValueError(f"the norm dims {ens['norm_dims']} are not one strided run of the inputs as they are stored")
+  return _hip.ENRG_LANES, EnergyArgs(ens['M'], devs[0].layout.stride(mdim), runs[0][0], runs[0][1], runs[1][1]), None
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -788,6 +823,8 @@ _KINDS = {
                   lambda d, out, dt, func, ens, cat:
                   ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
                                            int(bool(cat.right)), d[0], d[1], d[3], out))),
+    'enrg': _Kind(_enrg_operands, (),
+                  lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
 }
 
 
@@ -1493,7 +1530,10 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   wbx_contingency_partial: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
   cell * nthr + k, cell in (TP, FP, FN, TN)) / 'erps' (ranked probability score of an ensemble, wbx_ens_rps_partial: `cat` =
   {'p_thresholds', 't_thresholds' (float64 ndarrays of equal size, at most _hip.ERPS_MAX_THRESHOLDS), 'right_inclusive'},
-  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits).
+  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits) / 'enrg' (energy
+  score of an ensemble, wbx_ens_energy_partial: `ens` = {'member_dim', 'M', 'fair', 'norm_dims', 'norm_sizes'}, `dims` without the
+  member dim and the norm dims, which must be one strided run of both inputs; value lanes skill, spread; always stage 1, then
+  wbx_contract / wbx_contract_bits: no folded x weights, no binned route).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1527,7 +1567,7 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
     devs[3] = _mask_to_device(ctx, mask)
   if skipna:
     flags |= _hip.FLAG_SKIPNA
-  if ens and ens.get('fair', True):
+  if ens and (ens.get('fair', True) or ens.get('fair', True) is None):  # (None: an 'enrg' group no spread statistic has joined)
     flags |= _hip.FLAG_FAIR
   if ens and ens.get('skipna', False):
     flags |= _hip.FLAG_SKIPNA_ENS

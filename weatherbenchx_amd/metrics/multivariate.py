@@ -6,8 +6,10 @@ arithmetic on whatever holds the payload (NumPy on the host, torch where a chunk
 masked means are the Aggregator's reduction -- the same kernels as every other statistic.  `metrics.probabilistic` hands these
 names on, so `probabilistic.EnergyScore` etc. resolve as in the reference.
 
-One exception: EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own,
-wbx_ens_rps_partial (lazy.ens_rps_statistic); its per-point values are still this arithmetic.
+Two exceptions, both in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
+EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own, wbx_ens_rps_partial
+(lazy.ens_rps_statistic); EnergyScoreSkill and EnergyScoreSpread of one (predictions, targets) pair -- EnergyScore,
+TiledEnergyScore -- by one launch of wbx_ens_energy_partial (lazy.energy_statistic).
 """
 from __future__ import annotations
 
@@ -115,6 +117,43 @@ class EnsembleRankedProbabilityScore(base.PerVariableStatistic):
     return lazy.ens_rps_statistic(p, t, e, pa, tb, self._fair, self._right_inclusive, bin_dim=self._bin_dim)
 
 
+def _fused_energy(lane: int, predictions, targets, dim, ensemble_dim: str, fair):
+  """The skill (lane 0) or spread (lane 1) of the energy score as a lazy statistic that the Aggregator reduces with
+  wbx_ens_energy_partial (lazy.energy_statistic), or None where the host route has to do it: the switch is off, no device, other
+  dtypes than float32 / float64, no member dim in the predictions or one in the targets, a norm dim that one input lacks, norm dims
+  that are not one strided run of an input as a launch sees it, targets with a dim of their own, nothing left of the frame, a
+  `mask` coordinate along a norm or member dim, or an ensemble size the kernel does not take."""
+  if not lazy.FUSED_ENERGY:
+    return None
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  e, norm = ensemble_dim, _dims_tuple(dim)
+  if e not in p.dims or e in t.dims or e in norm or not norm or len(set(norm)) != len(norm):
+    return None
+  if any(d not in p.dims or d not in t.dims or p.sizes[d] != t.sizes[d] for d in norm):
+    return None
+  if str(p.dtype) not in ('float32', 'float64') or str(t.dtype) not in ('float32', 'float64'):
+    return None
+  if not set(t.dims) <= set(p.dims) or not set(p.dims) - {e} - set(norm):
+    return None
+  if not 2 <= p.sizes[e] <= _hip.ENRG_MAX_MEMBERS:
+    return None
+  for da in (p, t):
+    if 'mask' in da.coords and set(da.coords['mask'].dims) & ({e} | set(norm)):
+      return None
+    if engine.norm_run(lazy.payload_layout(da), norm, da.sizes) is None:
+      return None
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+    return None
+  if not engine.ens_energy_available(ctx):
+    return None
+  try:
+    return lazy.energy_statistic(lane, p, t, e, norm, fair)
+  except lazy._NeedsAlignment:  # pylint: disable=protected-access  (labels that differ: the host route joins them)
+    return None
+
+
 class EnergyScoreSkill(base.PerVariableStatistic):
   """mean_m ||X_m - Y|| with the norm over `dim` (probabilistic.py:480-503)."""
 
@@ -127,6 +166,11 @@ class EnergyScoreSkill(base.PerVariableStatistic):
     return f'EnergyScore_Skill_dim={self._dim}_ensemble_dim={self._ensemble_dim}'
 
   def _compute_per_variable(self, predictions, targets):
+    fused = _fused_energy(lazy.ENERGY_LANE['EnergyScoreSkill'], predictions, targets, self._dim, self._ensemble_dim, None)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The score as labelled-array arithmetic on whatever holds the payload."""
     return _norm_over(predictions - targets, _dims_tuple(self._dim)).mean(self._ensemble_dim, skipna=False)
 
 
@@ -146,6 +190,11 @@ class EnergyScoreSpread(base.PerVariableStatistic):
     return f'EnergyScore_Spread_dim={self._dim}_ensemble_dim={self._ensemble_dim}_fair={self._fair}'
 
   def _compute_per_variable(self, predictions, targets):
+    fused = _fused_energy(lazy.ENERGY_LANE['EnergyScoreSpread'], predictions, targets, self._dim, self._ensemble_dim, self._fair)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The score as labelled-array arithmetic on whatever holds the payload: one pass per cyclic member offset."""
     del targets
     e = self._ensemble_dim
     m = predictions.sizes[e]

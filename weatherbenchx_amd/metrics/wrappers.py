@@ -610,4 +610,13 @@ class Tile(InputTransform):
     return f'tiled_window_size_{self._window_size}_wrap_{self._wrap_longitude}_dim_{self._window_dim}'
 
   def transform_fn(self, da: xr.DataArray) -> xr.DataArray:
-    return construct_tiles(da, window_size=self._window_size, window_dim=self._window_dim, wrap_longitude=self._wrap_longitude)
+    # one tiled object per source object and setting: the statistics of a metric that tile the same inputs (TiledEnergyScore's
+    # skill and spread) then meet in one fused group -- and the windows are stacked once
+    if not isinstance(da, xr.DataArray):
+      return construct_tiles(da, window_size=self._window_size, window_dim=self._window_dim, wrap_longitude=self._wrap_longitude)
+    key = (self._window_size, self._window_dim, bool(self._wrap_longitude), da.__dict__.get('_mutations', 0))
+    cache = da.__dict__.setdefault('_wbx_tiles', {})
+    if key not in cache:
+      cache.clear()
+      cache[key] = construct_tiles(da, window_size=self._window_size, window_dim=self._window_dim, wrap_longitude=self._wrap_longitude)
+    return cache[key]

@@ -297,8 +297,9 @@ class DataArray:
   @property
   def values(self) -> np.ndarray:
     out = _to_numpy(self.data)
-    if isinstance(out, np.ndarray) and out.flags.writeable and (self.__dict__.get('_wbx_dev') or self.__dict__.get('_wbx_groups')):
-      # an uploaded copy of this payload, or a fused group whose (lazy or finished) statistics read it, is cached on the
+    if isinstance(out, np.ndarray) and out.flags.writeable and (self.__dict__.get('_wbx_dev') or self.__dict__.get('_wbx_groups')
+                                                                  or self.__dict__.get('_wbx_tiles')):
+      # an uploaded copy of this payload, a fused group whose (lazy or finished) statistics read it, or its tiled windows are cached on the
       # object -- other engine caches (weight products, tokens) do not depend on the payload --: a write through
       # `.values[...] = x` would leave it stale without anybody noticing, so the array is handed out as a read-only VIEW
       # (the caller's own array is not frozen) and the write fails loudly; `da[...] = x` is the mutation that drops the caches
