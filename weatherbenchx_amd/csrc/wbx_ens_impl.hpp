@@ -157,8 +157,10 @@ struct EnsOpF32 {
   // FAST32: the fp32 chain sums (stats32) -- the pipelined kernel only.  In s1_xr / s1_xk / s1_xf1 (no prefetch, 64-bit vector
   // addresses) they measured SLOWER than the fp64 sums (37-level field, same box: 1.57 against 1.40 ms on longitude-fastest,
   // 1.73 against 1.44 ms on latitude-fastest data: 162 instead of 133 VGPRs), while ens_pipe_kernel gains 9 % (1.39 -> 1.27 ms).
-  template <bool FAST32 = false>
-  __device__ __forceinline__ static bool compute(const S1Args& a, Regs& r, double (&val)[NLANE]) {
+  // HALVES (ens_pipe_kernel's paired blocks): with `halves` set the wave holds points of two rows, lanes 0-31 of one and lanes
+  // 32-63 of the other, and each half decides on its own points alone -- a row's values never depend on its neighbour's.
+  template <bool FAST32 = false, bool HALVES = false>
+  __device__ __forceinline__ static bool compute(const S1Args& a, Regs& r, double (&val)[NLANE], bool halves = false) {
     const int M = EXACT ? MP : a.M;
     const double td = (double)r.t;
     float(&xm)[MP] = r.xm;
@@ -292,7 +294,13 @@ struct EnsOpF32 {
       const float range = xm[MP - 1] - xm[0];
       const float big = fmaxf(fmaxf(fabsf(xm[0]), fabsf(xm[MP - 1])), fabsf(r.t));
       const bool fast_ok = (range == 0.f || (range >= 0x1p-50f && range <= 0x1p60f)) && big <= 0x1p100f;
-      redo = __builtin_amdgcn_ballot_w64(!fast_ok) != 0;
+      if constexpr (HALVES) {
+        const uint64_t bad = __builtin_amdgcn_ballot_w64(!fast_ok);
+        const uint32_t mine = threadIdx.x < 32 ? (uint32_t)bad : (uint32_t)(bad >> 32);
+        redo = halves ? mine != 0 : bad != 0;
+      } else {
+        redo = __builtin_amdgcn_ballot_w64(!fast_ok) != 0;
+      }
       if (!redo) stats32(a, xm, r.t, poison, val);
       r.poison = poison;
     } else {
@@ -597,7 +605,24 @@ constexpr int ENS_PIPE_WAVES = 3;   // waves per SIMD the register budget is cut
 //  coefficients it is 151 registers and runs three: 0.423 -> 0.378 ms on the 1.73 GB variable, 51 -> 57 % of the HBM peak; with the
 //  missing members replaced by the shift itself -- no per-member select, no class tests -- 113 registers, 0.336 ms = 64 %)
 constexpr int ENS_PIPE_SKIPNA_WAVES = 3;
-template <int MP, bool EXACT, int ALGO, bool FLAT>
+//
+// PAIR: two (key, chunk) indices per block, for launches whose every (key, chunk) is ONE row of nx = 64 q + 32 points
+// (launch_ens_pipe decides; R = the number of indices).  Such a row takes q + 1 tiles on its own, and the last of them sorts 32
+// clamped copies of the row's last point only to count them out again: 1 tile in 23 of a 1440-point row.  Block j owns the
+// indices A = 2 j and B = 2 j + 1 and walks them as ONE sequence of 2 q + 1 tiles without a clamped lane:
+//   A's q full tiles | the junction: lanes 0-31 = A's last 32 points, lanes 32-63 = B's first 32 | B's q full tiles from point 32.
+// (The last block of an odd launch owns A alone: its junction is today's half tile.)  One set of accumulators: at the junction
+// lanes 0-31 are added, row A's five wave sums are taken and stored, the accumulators are zeroed and lanes 32-63 are added.
+// Every partial is BIT FOR BIT what the one-index block writes: B's point p sits in lane (p + 32) % 64 = (p % 64) ^ 32, each
+// lane adds its points in the same order as before (a lane without a term at the junction adds +0.0, as the half tile did),
+// and wave_sum is an xor butterfly, whose every lane holds the same total under an xor relabelling of the lanes because
+// a + b == b + a.  The junction's LDS-DMA loads take a per-lane 64-bit address (one VGPR pair, stepped by the member stride:
+// 50 vector adds in 1 tile of 45) instead of SGPR base + shared offset.  A per-lane 32-bit offset from A's base would tie
+// eligibility to the distance of the two rows for every member; two EXEC halves with an SGPR base each put the scalar member
+// pointer into divergent control flow, which the padded buckets (`m < M` around every load) do not compile.  Registers:
+// ens_pipe_kernel<51, true, SORT, false, true> takes fewer VGPRs than the one-index instantiation (no clamps, no segment state).
+// The fp64 escape is decided per half at the junction (compute<.., HALVES>) and re-reads its points from the lane's own row.
+template <int MP, bool EXACT, int ALGO, bool FLAT, bool PAIR = false>
 __global__ void __launch_bounds__(64, ALGO == WBX_ENS_SKIPNA_SORT ? ENS_PIPE_SKIPNA_WAVES : ENS_PIPE_WAVES)
 ens_pipe_kernel(S1Args a, int R) {
   using Op = EnsOpF32<MP, EXACT, ALGO>;
@@ -607,6 +632,120 @@ ens_pipe_kernel(S1Args a, int R) {
   __shared__ float stage[NLDS][64];
   const int lane = threadIdx.x;
   const int M = EXACT ? MP : a.M;
+  if constexpr (PAIR) {
+    static_assert(!FLAT && ALGO == WBX_ENS_SORT, "paired rows: the plain rank-form sweep only");
+    const int nx = (int)a.nx;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&stage[0][0];
+    const int64_t mstride_b = a.mstride * 4;
+    const int64_t j = blockIdx.x;
+    const bool has_b = j < R;                // R pairs first, then one index per block
+    const int64_t ia = has_b ? 2 * j : j + R;
+    const int64_t ib = has_b ? ia + 1 : ia;  // (alone: "B" is A again, its lanes re-read A's last point and are counted out)
+    int64_t roa[WBX_MAX_INPUTS], rob[WBX_MAX_INPUTS];
+    {
+      int64_t kb[WBX_MAX_INPUTS];
+      const int64_t ka = ia / a.nchunk, kbk = ib / a.nchunk;
+      key_bases<2>(a, ka, kb);
+      row_bases<2>(a, kb, ka, (ia - ka * a.nchunk) * a.dchunk, roa);
+      key_bases<2>(a, kbk, kb);
+      row_bases<2>(a, kb, kbk, (ib - kbk * a.nchunk) * a.dchunk, rob);
+    }
+    const int q = nx >> 6;                   // full tiles per row; tile q is the junction
+    const int ntile = has_b ? 2 * q + 1 : q + 1;
+    const bool hi = lane >= 32;
+    // the junction's point of this lane, in its own row
+    const int ejn = hi ? (has_b ? lane - 32 : nx - 1) : nx - 32 + lane;
+
+    float xn[NREG > 0 ? NREG : 1], tn = 0.f;
+    auto lds_loads = [&](const int64_t ro0, const uint32_t voff) {
+      const char* um = uniform_ptr(reinterpret_cast<const char*>(a.in[0]) + ro0 * 4);
+#pragma unroll
+      for (int m = 0; m < NLDS; ++m) {
+        if (EXACT || m < M)
+          asm volatile("s_add_u32 m0, %2, %3\n\tglobal_load_lds_dword %0, %1 nt" ::"v"(voff), "s"(um), "s"(lds0), "i"(m * 256)
+                       : "memory", "scc", "m0");
+        um += mstride_b;
+        asm volatile("" : "+s"(um));
+      }
+    };
+    auto issue = [&](const int t) {  // tile t of the block's sequence
+      int64_t e, r0, r1;
+      if (t == q) {
+        e = ejn;
+        r0 = hi ? rob[0] : roa[0];
+        r1 = hi ? rob[1] : roa[1];
+        // two rows in one wave: the address is a 64-bit VGPR pair per lane, stepped per member
+        uint64_t vp = (uint64_t)(reinterpret_cast<const float*>(a.in[0]) + r0 + e * a.xstride[0]);
+#pragma unroll
+        for (int m = 0; m < NLDS; ++m) {
+          if (EXACT || m < M)
+            asm volatile("s_add_u32 m0, %1, %2\n\tglobal_load_lds_dword %0, off nt" ::"v"(vp), "s"(lds0), "i"(m * 256)
+                         : "memory", "scc", "m0");
+          vp += (uint64_t)mstride_b;
+          asm volatile("" : "+v"(vp));  // one add per member on the one pair, not 50 addresses kept in registers
+        }
+      } else {
+        const bool in_a = t < q;
+        e = (in_a ? 64 * t : 64 * (t - q) - 32) + lane;
+        r0 = in_a ? roa[0] : rob[0];
+        r1 = in_a ? roa[1] : rob[1];
+        lds_loads(r0, (uint32_t)e * (uint32_t)a.xstride[0] * 4u);
+      }
+      const float* pr = reinterpret_cast<const float*>(a.in[0]) + r0 + e * a.xstride[0];
+#pragma unroll
+      for (int m = NLDS; m < MP; ++m) xn[m - NLDS] = (EXACT || m < M) ? ld_stream(pr + (int64_t)m * a.mstride) : INFINITY;
+      tn = ld_stream(reinterpret_cast<const float*>(a.in[1]) + r1 + e * a.xstride[1]);
+    };
+    auto flush = [&](const int64_t idx, const double (&acc)[NA]) {
+#pragma unroll
+      for (int l = 0; l < NA; ++l) {
+        const double v = wave_sum(acc[l]);
+        if (lane == l) a.out[idx * NA + l] = v;
+      }
+    };
+
+    double acc[NA];
+#pragma unroll
+    for (int l = 0; l < NA; ++l) acc[l] = 0.0;
+    issue(0);
+    for (int t = 0; t < ntile; ++t) {
+      typename Op::Regs r;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int m = 0; m < NLDS; ++m) r.xm[m] = (EXACT || m < M) ? stage[m][lane] : INFINITY;
+#pragma unroll
+      for (int m = NLDS; m < MP; ++m) r.xm[m] = xn[m - NLDS];
+      r.t = tn;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this tile has left the staging buffer
+      if (t + 1 < ntile) issue(t + 1);
+      const bool jn = t == q;
+      double val[Op::NLANE];
+      if (Op::template compute<true, true>(a, r, val, jn)) {  // the fp64 escape: this lane's point, re-read from its own row
+        const bool in_b = jn ? hi : t > q;
+        int64_t rocur[WBX_MAX_INPUTS];
+#pragma unroll
+        for (int i = 0; i < WBX_MAX_INPUTS; ++i) rocur[i] = in_b ? rob[i] : roa[i];
+        const int64_t xcur = jn ? ejn : (t < q ? 64 * t : 64 * (t - q) - 32) + lane;
+        EnsOpGeneric<float>::values(a, rocur, xcur, val);
+        Op::apply_poison(r, val);
+      }
+      if (!jn) {
+#pragma unroll
+        for (int l = 0; l < NA; ++l) acc[l] += val[l];
+      } else {
+#pragma unroll
+        for (int l = 0; l < NA; ++l) acc[l] += hi ? 0.0 : val[l];
+        flush(ia, acc);
+#pragma unroll
+        for (int l = 0; l < NA; ++l) {
+          acc[l] = 0.0;
+          acc[l] += (hi && has_b) ? val[l] : 0.0;
+        }
+      }
+    }
+    if (has_b) flush(ib, acc);
+    return;
+  }
   const int64_t b = blockIdx.x;
   const int64_t key = b / a.nchunk;
   const int chunk = (int)(b - key * a.nchunk);
@@ -757,6 +896,22 @@ template <int MP, bool EXACT, int ALGO, bool FLAT = false>
 int launch_ens_pipe(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a) {
   const int64_t grid = plan->nkey * plan->nchunk;
   WBX_REQUIRE(grid < (int64_t)1 << 31, "grid too large (%lld blocks)", (long long)grid);
+  if constexpr (!FLAT && ALGO == WBX_ENS_SORT) {
+    // every (key, chunk) one row of 64 q + 32 points: two of them per block (see ens_pipe_kernel, PAIR).  The plan, the
+    // partial layout and every partial's bits are those of the one-index launch below.
+    // (chunks may cover more than the depth: every chunk has to own a row that exists)
+    const bool one_row = (a.D == 1 && a.nchunk == 1) || (a.dchunk == 1 && a.nchunk == a.D);
+    // Half as many blocks live twice as long, and so does the last, partly empty round: the rows of the last two rounds of
+    // resident waves keep a block each, the rows in front of them go in pairs.
+    const int64_t tail = 2 * (int64_t)ctx->num_cus * 4 * ENS_PIPE_WAVES;
+    const int64_t npair = one_row && a.nx % 64 == 32 && grid > tail ? (grid - tail) / 2 : 0;
+    if (npair > 0) {
+      hipLaunchKernelGGL((ens_pipe_kernel<MP, EXACT, ALGO, false, true>), dim3((unsigned)(grid - npair)), dim3(64), 0, ctx->stream,
+                         a, (int)npair);
+      WBX_HIP(hipGetLastError());
+      return 0;
+    }
+  }
   hipLaunchKernelGGL((ens_pipe_kernel<MP, EXACT, ALGO, FLAT>), dim3((unsigned)grid), dim3(64), 0, ctx->stream, a,
                      FLAT ? plan->plane_rows : 0);
   WBX_HIP(hipGetLastError());
