@@ -429,6 +429,39 @@ int wbx_ens_energy_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* W
                            int64_t L, int64_t p_norm_stride, int64_t t_norm_stride, const void* p, const void* t,
                            const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: variogram score of an ensemble (joined ABI 13) -----------------------------------------------------
+ * VariogramScore (probabilistic.py:554-600) of an ensemble of predictions against a target, in one pass over p and t instead of one
+ * whole-array pass per cyclic offset along the score's dim.  p has a member axis of length M and element stride `member_stride`,
+ * and p and t have a run of L elements with element strides `p_run_stride` / `t_run_stride` (the score's dim; a negative stride
+ * walks down from the first element the plan's offsets name); neither is part of key / depth / x.  Per point, with members x_m in
+ * R^L and target y in R^L:
+ *     VS = sum_{i, j in [0, L)} ( |y_i - y_j|^p - (1 / M) sum_m |x_i^m - x_j^m|^p )^2
+ * over ordered pairs, the diagonal included, which is 0 for finite values and NaN otherwise: a point with ANY NaN or infinite value
+ * among its (M + 1) L inputs is NaN (the kernel decides that with a flag per point, not by propagation), every other point is
+ * twice the sum over i < j.  L = 1 gives 0 (or NaN).  `power` is a code for p, there is no general pow: WBX_VGRAM_POW_HALF (0.5),
+ * WBX_VGRAM_POW_ONE (1), WBX_VGRAM_POW_TWO (2).
+ * Differences are formed in the input type; |d|^p in the input type: a correctly rounded square root of |d|, |d| itself, or one
+ * rounded product.  Everything from the member sum onwards is float64: the M terms in member order, the division by M, the
+ * difference with the target's term, the square, the pair sum in a fixed order.  No moment identity is used.
+ * ONE value lane (WBX_VGRAM_LANES).  Count lanes follow the library's convention (none / one under a mask / one under skipna): without
+ * flags a NaN point poisons its partial; under WBX_FLAG_MASKED alone a point contributes exactly 0 where the mask is 0 and poisons
+ * where it is not; under WBX_FLAG_SKIPNA a NaN point is counted out.  partial_out[nkey][nchunk][lanes_total][nj] as for
+ * wbx_det_partial: wbx_s1_partial_len with lanes = 1, wbx_contract and wbx_contract_bits serve it unchanged.  The result is a
+ * function of the inputs and the plan only, bit for bit: every sum is formed in a fixed order, nothing is added atomically.
+ * Refused (WBX_ERR_INVALID, output untouched): M outside 1..WBX_VGRAM_MAX_MEMBERS, L outside 1..WBX_VGRAM_MAX_RUN, an unknown power
+ * code or dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, plane_rows != 0 or x_weights.  vec = 4 is accepted
+ * and ignored; block_threads sets the x a block covers when x is kept, an x-summed launch always runs 256 threads.  nkey == 0
+ * touches nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_VGRAM_LANES 1
+#define WBX_VGRAM_MAX_MEMBERS 64
+#define WBX_VGRAM_MAX_RUN 64 /* the run is resident whole: 2016 pairs per point */
+#define WBX_VGRAM_POW_HALF 0
+#define WBX_VGRAM_POW_ONE 1
+#define WBX_VGRAM_POW_TWO 2
+int wbx_ens_variogram_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                              int64_t L, int64_t p_run_stride, int64_t t_run_stride, int power /* WBX_VGRAM_POW_* */, const void* p,
+                              const void* t, const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -648,7 +681,8 @@ typedef enum wbx_fn {
   WBX_FN_CONTRACT = 6, WBX_FN_CONTRACT_BITS = 7, WBX_FN_DET_BINNED = 8, WBX_FN_ENS_BINNED = 9, WBX_FN_ZONAL_SPECTRUM = 10,
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
-  WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22
+  WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
+  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -27,6 +27,11 @@ ERPS_MAX_MEMBERS = 256  # (WBX_ERPS_MAX_MEMBERS: a point's integer numerator fit
 ENRG_LANES = 2  # wbx_ens_energy_partial: skill, spread (WBX_ENRG_LANES)
 ENRG_MAX_MEMBERS = 64  # (WBX_ENRG_MAX_MEMBERS)
 ENRG_LDS_CHUNK = 16  # elements of the norm run the kernel stages at a time (csrc/wbx_ens_energy.hip: ENRG_LC)
+VGRAM_LANES = 1  # wbx_ens_variogram_partial (WBX_VGRAM_LANES)
+VGRAM_MAX_MEMBERS = 64  # (WBX_VGRAM_MAX_MEMBERS)
+VGRAM_MAX_RUN = 64  # elements along the score's dim: the run is resident whole (WBX_VGRAM_MAX_RUN)
+VGRAM_POW_HALF, VGRAM_POW_ONE, VGRAM_POW_TWO = 0, 1, 2  # the `power` codes (WBX_VGRAM_POW_*)
+VGRAM_POWERS = {0.5: VGRAM_POW_HALF, 1.0: VGRAM_POW_ONE, 2.0: VGRAM_POW_TWO}  # the exponents the kernel takes
 ENS_LANES = 5
 ENS2_LANES = 2  # wbx_ens2_partial: skill over (prediction, target) member pairs, unbiased MSE with both ensembles' counts
 ENS_SORT, ENS_PAIRWISE = 0, 1
@@ -48,6 +53,7 @@ EXPORTED_SYMBOLS = (
     'wbx_acc_reset', 'wbx_det_spectrum', 'wbx_det_spectrum_slabs', 'wbx_ens_binned', 'wbx_ens_binned_atoms_size', 'wbx_ens_binned_atoms',
     'wbx_ens2_partial', 'wbx_cat_exceed_field', 'wbx_chunk_replay', 'wbx_host_transpose', 'wbx_clock_probe', 'wbx_det_spectrum_folded',
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
+    'wbx_ens_variogram_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -55,7 +61,8 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_contract': 6, 'wbx_contract_bits': 7, 'wbx_det_binned': 8, 'wbx_ens_binned': 9, 'wbx_zonal_spectrum': 10,
           'wbx_zonal_spectrum_slabs': 11, 'wbx_det_spectrum': 12, 'wbx_det_spectrum_slabs': 13, 'wbx_acc_add': 14,
           'wbx_memset': 15, 'wbx_memcpy_d2d': 16, 'wbx_ctx_wait_fence': 17, 'wbx_fence_record': 18, 'wbx_det_spectrum_folded': 19,
-          'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22}
+          'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
+          'wbx_ens_variogram_partial': 23}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -70,6 +77,17 @@ def enrg_tile_points(m: int, threads: int) -> int:
   mp = (m + 4) // 4 * 4
   nblk = (mp // 4) * (mp // 4 + 1) // 2
   return max(1, min(64, 416 // mp, 3 * threads // nblk))
+
+
+def vgram_tile_points(l: int) -> int:
+  """Adjacent x positions one block of wbx_ens_variogram_partial stages at a time (csrc/wbx_ens_variogram.hip: vgrm_tile_points)."""
+  npair = l * (l - 1) // 2
+  return max(1, min(64, 2048 // npair if npair else 64, 512 // l))
+
+
+def vgram_member_chunk(m: int, l: int) -> int:
+  """Members that kernel stages at a time (vgrm_member_chunk)."""
+  return min(m, 6144 // (vgram_tile_points(l) * l))
 
 
 class CallStruct(C.Structure):  # wbx_call
@@ -211,6 +229,7 @@ def load_library():
         'wbx_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, vp, vp, vp, vp, vp],
         'wbx_ens_rps_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp],
         'wbx_ens_energy_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, vp, vp, vp, vp],
+        'wbx_ens_variogram_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, i32, vp, vp, vp, vp],
         'wbx_det_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, vp, vp, vp, vp],
         'wbx_ens_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp],
         'wbx_zonal_spectrum': [vp, vp, i64, i64, i64, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp],

@@ -465,6 +465,16 @@ def ens_energy_available(ctx) -> bool:
     return False
 
 
+def ens_variogram_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_variogram_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_variogram_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -743,6 +753,7 @@ CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
+VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -796,6 +807,20 @@ def _enrg_operands(ctx, devs, func, ens, cat, mdim):
   return _hip.ENRG_LANES, EnergyArgs(ens['M'], devs[0].layout.stride(mdim), runs[0][0], runs[0][1], runs[1][1]), None
 
 
+def _vgrm_operands(ctx, devs, func, ens, cat, mdim):
+  if not 1 <= int(ens['M']) <= _hip.VGRAM_MAX_MEMBERS:
+    raise ValueError(f"one variogram score launch takes 1..{_hip.VGRAM_MAX_MEMBERS} members (got {ens['M']})")
+  if float(ens['power']) not in _hip.VGRAM_POWERS:
+    raise ValueError(f"one variogram score launch takes p in {sorted(_hip.VGRAM_POWERS)} (got {ens['power']})")
+  runs = [norm_run(devs[i].layout, ens['norm_dims'], ens['norm_sizes']) for i in (0, 1)]
+  if runs[0] is None or runs[1] is None:
+    raise ValueError(f"the dim {ens['norm_dims']} is not one strided run of the inputs as they are stored")
+  if not 1 <= runs[0][0] <= _hip.VGRAM_MAX_RUN:
+    raise ValueError(f'one variogram score launch takes a run of 1..{_hip.VGRAM_MAX_RUN} elements (got {runs[0][0]})')
+  return _hip.VGRAM_LANES, VariogramArgs(ens['M'], devs[0].layout.stride(mdim), runs[0][0], runs[0][1], runs[1][1],
+                                         _hip.VGRAM_POWERS[float(ens['power'])]), None
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -825,6 +850,8 @@ _KINDS = {
                                            int(bool(cat.right)), d[0], d[1], d[3], out))),
     'enrg': _Kind(_enrg_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
+    'vgrm': _Kind(_vgrm_operands, (),
+                  lambda d, out, dt, func, ens, cat: ('wbx_ens_variogram_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
 }
 
 
@@ -1533,7 +1560,10 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits) / 'enrg' (energy
   score of an ensemble, wbx_ens_energy_partial: `ens` = {'member_dim', 'M', 'fair', 'norm_dims', 'norm_sizes'}, `dims` without the
   member dim and the norm dims, which must be one strided run of both inputs; value lanes skill, spread; always stage 1, then
-  wbx_contract / wbx_contract_bits: no folded x weights, no binned route).
+  wbx_contract / wbx_contract_bits: no folded x weights, no binned route) / 'vgrm' (variogram score of an ensemble,
+  wbx_ens_variogram_partial: `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag), 'norm_dims' (the score's one
+  dim), 'norm_sizes', 'power'}, `dims` without the member dim and that dim, which must be one strided run of both inputs; one
+  value lane; the same stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;

@@ -6,10 +6,11 @@ arithmetic on whatever holds the payload (NumPy on the host, torch where a chunk
 masked means are the Aggregator's reduction -- the same kernels as every other statistic.  `metrics.probabilistic` hands these
 names on, so `probabilistic.EnergyScore` etc. resolve as in the reference.
 
-Two exceptions, both in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
+Three exceptions, all in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
 EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own, wbx_ens_rps_partial
 (lazy.ens_rps_statistic); EnergyScoreSkill and EnergyScoreSpread of one (predictions, targets) pair -- EnergyScore,
-TiledEnergyScore -- by one launch of wbx_ens_energy_partial (lazy.energy_statistic).
+TiledEnergyScore -- by one launch of wbx_ens_energy_partial (lazy.energy_statistic); VariogramScore -- TiledVariogramScore -- at
+p = 0.5, 1 or 2 by one launch of wbx_ens_variogram_partial (lazy.variogram_statistic).
 """
 from __future__ import annotations
 
@@ -210,6 +211,49 @@ class EnergyScoreSpread(base.PerVariableStatistic):
       return total / float(m * (m - 1) if self._fair else m * m)
 
 
+def _fused_variogram(predictions, targets, dim, ensemble_dim: str, power):
+  """The variogram score as a lazy statistic that the Aggregator reduces with wbx_ens_variogram_partial (lazy.variogram_statistic),
+  or None where the host route has to do it: the conditions of _fused_energy -- the switch is off, no device, other dtypes than
+  float32 / float64, no member dim in the predictions or one in the targets, a `dim` that one input lacks or that has two sizes,
+  a `dim` that is not one strided run of an input as a launch sees it, targets with a dim of their own, nothing left of the frame,
+  a `mask` coordinate along `dim` or the member dim, labels that differ -- and a power other than 0.5, 1 or 2, more than
+  _hip.VGRAM_MAX_RUN elements along `dim` or more than _hip.VGRAM_MAX_MEMBERS members."""
+  if not lazy.FUSED_VARIOGRAM:
+    return None
+  try:
+    if not isinstance(dim, str) or float(power) not in _hip.VGRAM_POWERS:
+      return None
+  except (TypeError, ValueError):
+    return None
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  e = ensemble_dim
+  if e not in p.dims or e in t.dims or e == dim:
+    return None
+  if dim not in p.dims or dim not in t.dims or p.sizes[dim] != t.sizes[dim]:
+    return None
+  if str(p.dtype) not in ('float32', 'float64') or str(t.dtype) not in ('float32', 'float64'):
+    return None
+  if not set(t.dims) <= set(p.dims) or not set(p.dims) - {e, dim}:
+    return None
+  if not 1 <= p.sizes[e] <= _hip.VGRAM_MAX_MEMBERS or not 1 <= p.sizes[dim] <= _hip.VGRAM_MAX_RUN:
+    return None
+  for da in (p, t):
+    if 'mask' in da.coords and set(da.coords['mask'].dims) & {e, dim}:
+      return None
+    if engine.norm_run(lazy.payload_layout(da), (dim,), da.sizes) is None:
+      return None
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+    return None
+  if not engine.ens_variogram_available(ctx):
+    return None
+  try:
+    return lazy.variogram_statistic(p, t, e, dim, power)
+  except lazy._NeedsAlignment:  # pylint: disable=protected-access  (labels that differ: the host route joins them)
+    return None
+
+
 class VariogramScore(base.PerVariableStatistic):
   """sum_{i, j} (|y_i - y_j|**p - mean_m |x_i^m - x_j^m|**p)**2 over all pairs along `dim` (Scheuerer & Hamill 2015;
   probabilistic.py:554-603).  Same pairing by cyclic offsets as EnergyScoreSpread: [N, N] tables are never formed."""
@@ -224,6 +268,11 @@ class VariogramScore(base.PerVariableStatistic):
     return f'VariogramScore_dim={self._dim}_ensemble_dim={self._ensemble_dim}'
 
   def _compute_per_variable(self, predictions, targets):
+    fused = _fused_variogram(predictions, targets, self._dim, self._ensemble_dim, self._p)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The score as labelled-array arithmetic on whatever holds the payload: one pass per cyclic offset along `dim`."""
     d, n = self._dim, predictions.sizes[self._dim]
     strip = lambda a: a.drop_vars([d]) if d in a.coords else a
     x, y = strip(predictions), strip(targets)
