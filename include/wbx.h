@@ -462,6 +462,37 @@ int wbx_ens_variogram_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /
                               int64_t L, int64_t p_run_stride, int64_t t_run_stride, int power /* WBX_VGRAM_POW_* */, const void* p,
                               const void* t, const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: Wasserstein-1 distance between two ensembles (joined ABI 13) ------------------------------------------
+ * WassersteinDistance (probabilistic.py) of an ensemble of predictions against an ensemble of targets, in one pass over p and t
+ * instead of a pooled float64 sort and two cumulative sums.  p has a member axis of length M and element stride `member_stride`, t
+ * one of length N and element stride `target_member_stride`; neither is part of key / depth / x, and the two sizes are independent.
+ * Per point, with the sorted members p_(0) <= ... <= p_(M-1) and t_(0) <= ... <= t_(N-1):
+ *     W1 = int_0^1 |Qp(u) - Qt(u)| du = ( sum over pieces of c |p_(i) - t_(j)| ) / (M N)
+ * The pieces are the M + N - gcd(M, N) intervals between consecutive breakpoints of {i / M} u {j / N}.  A piece's length is an
+ * integer in units of 1 / (M N): c = min((i + 1) N, (j + 1) M) - max(i N, j M); i advances when (i + 1) N <= (j + 1) M and j
+ * when (j + 1) M <= (i + 1) N, from i = j = 0.  The sequence (i, j, c) depends on (M, N) only, not on the data.
+ * Members are sorted in the input type (exact).  Differences, their absolute values, the products with the integer c and the sum are
+ * float64 -- the difference rounded once, the product added to the sum by one fused multiply-add --, the sum in the order of the
+ * walk; one division by (double)(M N) at the end.
+ * Non-finite members are what the reference's pooled form makes of them, decided by a flag per point and not by propagation: a
+ * NaN member on either side makes the point NaN; two or more +inf among the pooled M + N members make the point NaN, and so do two
+ * or more -inf (the pooled form has an inf - inf gap); otherwise the arithmetic decides -- a single +inf or a single -inf, or one
+ * of each, gives +inf.  (The walk alone would give +inf for p = [inf, inf], t = [0].)
+ * ONE value lane (WBX_WASS_LANES).  Count lanes follow the library's convention (none / one under a mask / one under skipna): without
+ * flags a NaN point poisons its partial; under WBX_FLAG_MASKED alone a point contributes exactly 0 where the mask is 0 and poisons
+ * where it is not; under WBX_FLAG_SKIPNA a NaN point is counted out.  partial_out[nkey][nchunk][lanes_total][nj] as for
+ * wbx_det_partial: wbx_s1_partial_len with lanes = 1, wbx_contract and wbx_contract_bits serve it unchanged.  The result is a
+ * function of the inputs and the plan only, bit for bit: every sum is formed in a fixed order, nothing is added atomically.
+ * Refused (WBX_ERR_INVALID, output untouched): M or N outside 1..WBX_WASS_MAX_MEMBERS, an unknown dtype, flags beyond
+ * MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, plane_rows != 0 or x_weights.  vec = 4 is accepted and ignored; a block runs
+ * block_threads threads up to what its LDS holds (128 for float32, 64 for float64).  nkey == 0 touches nothing; ndepth == 0 or
+ * nx == 0 zero the partial. */
+#define WBX_WASS_LANES 1
+#define WBX_WASS_MAX_MEMBERS 64 /* a side, the largest generated sorting network */
+int wbx_ens_wasserstein_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                                int N, int64_t target_member_stride, const void* p, const void* t, const uint8_t* mask,
+                                double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -682,7 +713,7 @@ typedef enum wbx_fn {
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
-  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23
+  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

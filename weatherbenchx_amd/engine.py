@@ -475,6 +475,16 @@ def ens_variogram_available(ctx) -> bool:
     return False
 
 
+def ens_wasserstein_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_wasserstein_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_wasserstein_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -821,6 +831,13 @@ def _vgrm_operands(ctx, devs, func, ens, cat, mdim):
                                          _hip.VGRAM_POWERS[float(ens['power'])]), None
 
 
+def _wass_operands(ctx, devs, func, ens, cat, mdim):
+  for side in ('M', 'N'):
+    if not 1 <= int(ens[side]) <= _hip.WASS_MAX_MEMBERS:
+      raise ValueError(f"one Wasserstein distance launch takes 1..{_hip.WASS_MAX_MEMBERS} members a side (got {ens['M']}, {ens['N']})")
+  return _hip.WASS_LANES, Ens2Args(ens['M'], devs[0].layout.stride(mdim), ens['N'], devs[1].layout.stride(mdim)), None
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -852,6 +869,8 @@ _KINDS = {
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
     'vgrm': _Kind(_vgrm_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_variogram_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
+    'wass': _Kind(_wass_operands, (),
+                  lambda d, out, dt, func, ens, cat: ('wbx_ens_wasserstein_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
 }
 
 
@@ -1563,6 +1582,8 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   wbx_contract / wbx_contract_bits: no folded x weights, no binned route) / 'vgrm' (variogram score of an ensemble,
   wbx_ens_variogram_partial: `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag), 'norm_dims' (the score's one
   dim), 'norm_sizes', 'power'}, `dims` without the member dim and that dim, which must be one strided run of both inputs; one
+  value lane; the same stage 2) / 'wass' (Wasserstein-1 distance between two ensembles, wbx_ens_wasserstein_partial: `ens` =
+  {'member_dim' (a dim of both inputs), 'M', 'N', 'fair': False (the entry takes no such flag)}, 1 <= M, N <= _hip.WASS_MAX_MEMBERS; one
   value lane; the same stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =

@@ -53,6 +53,9 @@ ENERGY_LANE = {'EnergyScoreSkill': 0, 'EnergyScoreSpread': 1}
 # False (WBX_FUSED_VARIOGRAM=0): VariogramScore (TiledVariogramScore) is labelled-array arithmetic on the host -- one whole-array pass
 # per cyclic offset along its dim -- and reduced as before wbx_ens_variogram_partial existed (A/B timing, tests).
 FUSED_VARIOGRAM = os.environ.get('WBX_FUSED_VARIOGRAM', '1') != '0'
+# False (WBX_FUSED_WASSERSTEIN=0): WassersteinDistance is a pooled float64 sort and two cumulative sums on the host, reduced as before
+# wbx_ens_wasserstein_partial existed (A/B timing, tests).
+FUSED_WASSERSTEIN = os.environ.get('WBX_FUSED_WASSERSTEIN', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -203,7 +206,7 @@ class FusedGroup:
     self.kind = kind
     self.p, self.t = p, t
     self.ens = ens  # {'member_dim', 'M'}; kind 'enrg': + {'fair' (None: no spread statistic has said yet), 'norm_dims', 'norm_sizes'};
-    # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}
+    # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}; kinds 'ens2', 'wass': + {'N'}
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
@@ -237,7 +240,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass'):
       return [self.p, self.t], 0
     if self.clim is not None:
       return [self.p, self.t, self.clim.source], _hip.DET6
@@ -251,7 +254,7 @@ class FusedGroup:
       ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                  skipna=skipna, clim=self.clim, ens=ens)
-    # 'ens2', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
+    # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
     # group are its own); 'cat', 'cont': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
                                                   skipna=skipna, ens=self.ens, cat=cat)
@@ -335,11 +338,17 @@ class FusedGroup:
       stat = multivariate.VariogramScore(dim=ens['norm_dims'][0], ensemble_dim=ens['member_dim'], p=ens['power'])
       out = stat.host_per_variable(self.p, self.t)
       return out.transpose(*self.dims).data
-    if self.kind == 'ens2':  # stage 1 with every dim kept IS the per-point statistic
+    if self.kind in ('ens2', 'wass'):  # stage 1 with every dim kept IS the per-point statistic
       with engine.synchronous_results():
         values, _, out_dims = self.reduce((), None, (), use_mask=False, skipna=False)
       arr = np.asarray(values, np.float64)[lane]
-      return np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims]))
+      arr = np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims]))
+      if self.kind == 'wass':  # a float64 tensor where a payload is one, on its device: the array type the host route gives
+        for da in (self.p, self.t):
+          if xr._is_torch(da.data):  # pylint: disable=protected-access
+            import torch  # pylint: disable=g-import-not-at-top
+            return torch.as_tensor(arr, device=da.data.device)
+      return arr
     inputs, func = self.inputs_and_func()
     ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
     gather, inputs = _gather_spec(self.clim, inputs, self.dims)
@@ -800,6 +809,19 @@ def variogram_statistic(p, t, ensemble_dim: str, dim: str, power) -> xr.DataArra
   ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': False, 'norm_dims': (dim,), 'norm_sizes': {dim: int(p.sizes[dim])},
          'power': power}
   grp = _group_for('vgrm', p, t, ens=ens, clim_key=('vgrm', dim, power))
+  return LazyStatistic(grp, 0, name=p.name)
+
+
+def wasserstein_statistic(p, t, ensemble_dim: str) -> xr.DataArray:
+  """WassersteinDistance between the ensembles `p` and `t`, each with its own size along `ensemble_dim`, as a LazyStatistic on a
+  FusedGroup of kind 'wass' (wbx_ens_wasserstein_partial), lane 0.  The (p, t) objects and the member dim key the group; its frame
+  drops the member dim.  Frames or labels that differ raise _NeedsAlignment: the caller keeps the host route, which broadcasts."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  for da in (p, t):
+    if ensemble_dim not in da.dims:
+      raise ValueError(f'Dimension {ensemble_dim} not found in {da.dims}')
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'N': t.sizes[ensemble_dim], 'fair': False}
+  grp = _group_for('wass', p, t, ens=ens, clim_key=('wass',))
   return LazyStatistic(grp, 0, name=p.name)
 
 

@@ -6,11 +6,12 @@ arithmetic on whatever holds the payload (NumPy on the host, torch where a chunk
 masked means are the Aggregator's reduction -- the same kernels as every other statistic.  `metrics.probabilistic` hands these
 names on, so `probabilistic.EnergyScore` etc. resolve as in the reference.
 
-Three exceptions, all in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
+Four exceptions, all in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
 EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own, wbx_ens_rps_partial
 (lazy.ens_rps_statistic); EnergyScoreSkill and EnergyScoreSpread of one (predictions, targets) pair -- EnergyScore,
 TiledEnergyScore -- by one launch of wbx_ens_energy_partial (lazy.energy_statistic); VariogramScore -- TiledVariogramScore -- at
-p = 0.5, 1 or 2 by one launch of wbx_ens_variogram_partial (lazy.variogram_statistic).
+p = 0.5, 1 or 2 by one launch of wbx_ens_variogram_partial (lazy.variogram_statistic); WassersteinDistance between ensembles of at
+most 64 members a side by one launch of wbx_ens_wasserstein_partial (lazy.wasserstein_statistic).
 """
 from __future__ import annotations
 
@@ -286,6 +287,46 @@ class VariogramScore(base.PerVariableStatistic):
     return total
 
 
+def _fused_wasserstein(predictions, targets, ensemble_dim: str):
+  """The Wasserstein distance as a lazy statistic that the Aggregator reduces with wbx_ens_wasserstein_partial
+  (lazy.wasserstein_statistic), or None where the host route has to do it: the switch is off, no device or library, or no such
+  symbol in it, a dtype other than float32 / float64 or two different dtypes, an ensemble of fewer than 1 or more than
+  _hip.WASS_MAX_MEMBERS members on either side, a `mask` coordinate along the member dim, nothing left of the frame without the
+  member dim, and frames or labels the launch cannot take as they stand where the host route broadcasts: a dim that one input
+  lacks, sizes or labels that differ, a coordinate the two inputs disagree about.  No shape class is kept from the kernel for
+  speed: it won at every shape that was measured."""
+  if not lazy.FUSED_WASSERSTEIN:
+    return None
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  e = ensemble_dim
+  if str(p.dtype) not in ('float32', 'float64') or str(t.dtype) != str(p.dtype):
+    return None
+  if not 1 <= p.sizes[e] <= _hip.WASS_MAX_MEMBERS or not 1 <= t.sizes[e] <= _hip.WASS_MAX_MEMBERS:
+    return None
+  frame = tuple(d for d in p.dims if d != e)
+  if not frame or set(frame) != set(t.dims) - {e}:
+    return None
+  for da in (p, t):
+    if 'mask' in da.coords and e in da.coords['mask'].dims:
+      return None
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+    return None
+  if not engine.ens_wasserstein_available(ctx):
+    return None
+  try:
+    stat = lazy.wasserstein_statistic(p, t, e)
+  except (lazy._NeedsAlignment, ValueError):  # pylint: disable=protected-access  (the host route broadcasts, or says what is wrong)
+    return None
+  # the host route hands on every coordinate of either input that lies in the frame, the predictions' first; a group drops what
+  # the two disagree about
+  want = {k for da in (p, t) for k, (cd, _) in da._coords.items() if k != e and set(cd) <= set(frame)}  # pylint: disable=protected-access
+  if stat.dims != frame or set(stat._coords) != want:  # pylint: disable=protected-access
+    return None
+  return stat
+
+
 class WassersteinDistance(base.PerVariableStatistic):
   """1-Wasserstein (earth mover's) distance between the prediction ensemble and the target ensemble at every point; the two
   ensembles may differ in size (probabilistic.py:785-833, there through scipy.stats.wasserstein_distance point by point).
@@ -306,6 +347,13 @@ class WassersteinDistance(base.PerVariableStatistic):
       raise ValueError(f'Ensemble dimension {e!r} not found in predictions: {predictions}')
     if e not in targets.dims:
       raise ValueError(f'Ensemble dimension {e!r} not found in targets: {targets}')
+    fused = _fused_wasserstein(predictions, targets, e)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The distance as array arithmetic on whatever holds the payload: a stable float64 sort of the pooled members, two
+    cumulative sums and the gaps between them."""
+    e = self._ensemble_dim
     strip = lambda a: a.drop_vars([e]) if e in a.coords else a
     p, t = xr.broadcast(strip(predictions).rename({e: '_p'}), strip(targets).rename({e: '_t'}))
     frame = tuple(d for d in p.dims if d not in ('_p', '_t'))
