@@ -493,6 +493,58 @@ int wbx_ens_wasserstein_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype
                                 int N, int64_t target_member_stride, const void* p, const void* t, const uint8_t* mask,
                                 double* partial_out);
 
+/* ---- stage 1: interval statistics of an ensemble (joined ABI 13) ----------------------------------------------------
+ * Covered, Confident and JaccardDistant (categorical.py:701-863, the factors of Opportunism) of an ensemble of predictions against
+ * a target and a climatology of two quantile fields, in one pass that sorts a point's members once, instead of two host quantile
+ * fields per statistic, an aligned copy of the climatology and one Boolean array per statistic.  p has a member axis of length M and
+ * element stride `member_stride`, which is not part of key / depth / x.  `c` is input 2 of the plan (key_off[2], depth_off[2],
+ * xstride[2], the gather tables; zero strides where it does not vary), and each bound's `c_off` is added to that address: the element
+ * offset of the bound's quantile label along the climatology's quantile dim.
+ * `lanes` is a set of WBX_IVL_* bits; the value lanes are the requested statistics in the order Covered, Confident, JaccardDistant.
+ * `params` is a HOST array of three wbx_ivl_lane in that order, read during the call (entries of lanes not asked for are ignored).
+ * Per point:
+ *   Members are sorted in the input type (exact).  Everything after the sort is float64, every product, sum and quotient rounded on
+ *   its own (no fused multiply-add).  A quantile bound (k, g) -- the host forms h = q (M - 1), k = floor(h), g = h - k in float64 --
+ *   is NumPy's `linear` method in NumPy's order of operations: with A = x_(k), B = x_(min(k + 1, M - 1)), d = B - A it is
+ *       A + d g         where g < 0.5,
+ *       B - d (1 - g)   otherwise,
+ *   with no shortcut for g == 0 (inf * 0 gives the NaN NumPy gives).  A NaN member makes every ensemble quantile of the point NaN,
+ *   by a flag gathered while the members are loaded and not by propagation; from there the formulas decide:
+ *     Covered        = lo <= t && t <= hi
+ *     Confident      = (hi - lo) < threshold * (c_hi - c_lo)
+ *     JaccardDistant = (1 - index) > threshold, with
+ *         overlap = max(min(a_hi, c_hi) - max(a_lo, c_lo), 0)   (min / max hand a NaN on, and so does the clip)
+ *         union   = (a_hi - a_lo) + (c_hi - c_lo) - overlap
+ *         index   = union > 0 ? overlap / union : 1             (false for a NaN union)
+ *   An indicator is 0 or 1, never NaN.
+ * Inputs that no requested lane needs are not read: t without Covered, c with Covered alone (c may then be NULL).
+ * Count lanes follow the library's convention (none / one under a mask / one per value lane under skipna); no value is NaN, so
+ * under WBX_FLAG_SKIPNA every unmasked point is counted, and under WBX_FLAG_MASKED a point contributes exactly 0 where the mask is 0.
+ * partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial: wbx_s1_partial_len with lanes = the number of bits set,
+ * wbx_contract and wbx_contract_bits serve it unchanged.  Every partial is an integer in float64 and a function of the inputs and
+ * the plan only: every sum is formed in a fixed order, nothing is added atomically.
+ * Refused (WBX_ERR_INVALID, output untouched): M outside 1..WBX_IVL_MAX_MEMBERS, `lanes` zero or beyond the three bits, a requested
+ * bound with k outside 0..M-1 or g outside [0, 1), an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, a
+ * requested lane whose input (t for Covered, c for the other two) is NULL, plane_rows != 0 or x_weights.  vec = 4 is accepted and
+ * ignored; a block runs block_threads threads up to what its LDS holds (128 for float32, 64 for float64).  nkey == 0 touches
+ * nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_IVL_COVERED 1
+#define WBX_IVL_CONFIDENT 2
+#define WBX_IVL_JACCARD 4
+#define WBX_IVL_MAX_MEMBERS 64 /* the largest generated sorting network */
+typedef struct wbx_ivl_bound {
+  int32_t k;     /* rank of the lower neighbour, 0..M-1 */
+  double g;      /* weight of the upper neighbour, [0, 1) */
+  int64_t c_off; /* element offset of the bound's quantile label in the climatology */
+} wbx_ivl_bound;
+typedef struct wbx_ivl_lane {
+  wbx_ivl_bound lo, hi;
+  double threshold; /* Confident: confidence_threshold; JaccardDistant: threshold; Covered: unused */
+} wbx_ivl_lane;
+int wbx_ens_interval_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                             int lanes /* WBX_IVL_* bit set */, const wbx_ivl_lane* params /* HOST, three entries */, const void* p,
+                             const void* t, const void* c, const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -713,7 +765,7 @@ typedef enum wbx_fn {
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
-  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24
+  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

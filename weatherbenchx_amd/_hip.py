@@ -34,6 +34,8 @@ VGRAM_POW_HALF, VGRAM_POW_ONE, VGRAM_POW_TWO = 0, 1, 2  # the `power` codes (WBX
 VGRAM_POWERS = {0.5: VGRAM_POW_HALF, 1.0: VGRAM_POW_ONE, 2.0: VGRAM_POW_TWO}  # the exponents the kernel takes
 WASS_LANES = 1  # wbx_ens_wasserstein_partial (WBX_WASS_LANES)
 WASS_MAX_MEMBERS = 64  # a side (WBX_WASS_MAX_MEMBERS)
+IVL_COVERED, IVL_CONFIDENT, IVL_JACCARD = 1, 2, 4  # wbx_ens_interval_partial: the `lanes` bits, in value-lane order (WBX_IVL_*)
+IVL_MAX_MEMBERS = 64  # (WBX_IVL_MAX_MEMBERS)
 ENS_LANES = 5
 ENS2_LANES = 2  # wbx_ens2_partial: skill over (prediction, target) member pairs, unbiased MSE with both ensembles' counts
 ENS_SORT, ENS_PAIRWISE = 0, 1
@@ -55,7 +57,7 @@ EXPORTED_SYMBOLS = (
     'wbx_acc_reset', 'wbx_det_spectrum', 'wbx_det_spectrum_slabs', 'wbx_ens_binned', 'wbx_ens_binned_atoms_size', 'wbx_ens_binned_atoms',
     'wbx_ens2_partial', 'wbx_cat_exceed_field', 'wbx_chunk_replay', 'wbx_host_transpose', 'wbx_clock_probe', 'wbx_det_spectrum_folded',
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
-    'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial',
+    'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -64,7 +66,7 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_zonal_spectrum_slabs': 11, 'wbx_det_spectrum': 12, 'wbx_det_spectrum_slabs': 13, 'wbx_acc_add': 14,
           'wbx_memset': 15, 'wbx_memcpy_d2d': 16, 'wbx_ctx_wait_fence': 17, 'wbx_fence_record': 18, 'wbx_det_spectrum_folded': 19,
           'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
-          'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24}
+          'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -90,6 +92,14 @@ def vgram_tile_points(l: int) -> int:
 def vgram_member_chunk(m: int, l: int) -> int:
   """Members that kernel stages at a time (vgrm_member_chunk)."""
   return min(m, 6144 // (vgram_tile_points(l) * l))
+
+
+class IvlBoundStruct(C.Structure):  # wbx_ivl_bound
+  _fields_ = [('k', C.c_int32), ('g', C.c_double), ('c_off', C.c_int64)]
+
+
+class IvlLaneStruct(C.Structure):  # wbx_ivl_lane
+  _fields_ = [('lo', IvlBoundStruct), ('hi', IvlBoundStruct), ('threshold', C.c_double)]
 
 
 class CallStruct(C.Structure):  # wbx_call
@@ -233,6 +243,7 @@ def load_library():
         'wbx_ens_energy_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, vp, vp, vp, vp],
         'wbx_ens_variogram_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, i32, vp, vp, vp, vp],
         'wbx_ens_wasserstein_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i64, vp, vp, vp, vp],
+        'wbx_ens_interval_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlLaneStruct), vp, vp, vp, vp, vp],
         'wbx_det_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, vp, vp, vp, vp],
         'wbx_ens_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp],
         'wbx_zonal_spectrum': [vp, vp, i64, i64, i64, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp],

@@ -12,6 +12,7 @@ import collections
 import contextlib
 import ctypes as C
 import dataclasses
+import math
 import os
 from typing import Sequence
 
@@ -485,6 +486,16 @@ def ens_wasserstein_available(ctx) -> bool:
     return False
 
 
+def ens_interval_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_interval_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_interval_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -764,6 +775,8 @@ ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
 VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
+IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
+IvlArgs = collections.namedtuple('IvlArgs', 'params')  # a HOST array of three _hip.IvlLaneStruct: no device buffer to keep
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -838,6 +851,42 @@ def _wass_operands(ctx, devs, func, ens, cat, mdim):
   return _hip.WASS_LANES, Ens2Args(ens['M'], devs[0].layout.stride(mdim), ens['N'], devs[1].layout.stride(mdim)), None
 
 
+IVL_BITS = {'Covered': _hip.IVL_COVERED, 'Confident': _hip.IVL_CONFIDENT, 'JaccardDistant': _hip.IVL_JACCARD}  # value-lane order
+
+
+def ivl_bound(q, m: int):
+  """(k, g) of the quantile level `q` of `m` sorted members, NumPy's `linear` method: h = q (m - 1), k = floor(h), g = h - k, all
+  float64 (include/wbx.h)."""
+  h = float(q) * (int(m) - 1)
+  k = math.floor(h)
+  return int(k), h - k
+
+
+def _ivl_operands(ctx, devs, func, ens, cat, mdim):
+  m = int(ens['M'])
+  if not 1 <= m <= _hip.IVL_MAX_MEMBERS:
+    raise ValueError(f'one interval statistics launch takes 1..{_hip.IVL_MAX_MEMBERS} members (got {m})')
+  lanes = int(cat['lanes'])
+  if not lanes or lanes & ~(_hip.IVL_COVERED | _hip.IVL_CONFIDENT | _hip.IVL_JACCARD):
+    raise ValueError(f'the lanes of an interval statistics launch are a non-empty set of IVL_* bits (got {lanes:#x})')
+  params = (_hip.IvlLaneStruct * 3)()
+  for slot, bit in enumerate(IVL_BITS.values()):
+    if not lanes & bit:
+      continue
+    lane = cat['params'][bit]  # {'bounds': (q_lo, q_hi), 'threshold', 'q_index': (positions along the quantile dim) or None}
+    needs_c = bit != _hip.IVL_COVERED
+    if needs_c and devs[2] is None:
+      raise ValueError('Confident and JaccardDistant need the climatology (input 2)')
+    for bound, q, j in zip((params[slot].lo, params[slot].hi), lane['bounds'], lane['q_index'] if needs_c else (0, 0)):
+      k, g = ivl_bound(q, m)
+      if not (0 <= k < m and 0.0 <= g < 1.0):
+        raise ValueError(f'quantile level {q!r} is outside [0, 1]')
+      bound.k, bound.g = k, g
+      bound.c_off = int(j) * devs[2].layout.stride(cat['quantile_dim']) if needs_c else 0
+    params[slot].threshold = float(lane['threshold']) if needs_c else 0.0
+  return bin(lanes).count('1'), IvlEnsArgs(m, devs[0].layout.stride(mdim), lanes), IvlArgs(params)
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -871,6 +920,9 @@ _KINDS = {
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_variogram_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
     'wass': _Kind(_wass_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_wasserstein_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
+    'ivl': _Kind(_ivl_operands, (),  # (the lane parameters are host values: a recorded chunk keeps the array itself)
+                 lambda d, out, dt, func, ens, cat:
+                 ('wbx_ens_interval_partial', (dt, *map(int, ens), cat.params, d[0], d[1], d[2], d[3], out))),
 }
 
 
@@ -1584,7 +1636,11 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   dim), 'norm_sizes', 'power'}, `dims` without the member dim and that dim, which must be one strided run of both inputs; one
   value lane; the same stage 2) / 'wass' (Wasserstein-1 distance between two ensembles, wbx_ens_wasserstein_partial: `ens` =
   {'member_dim' (a dim of both inputs), 'M', 'N', 'fair': False (the entry takes no such flag)}, 1 <= M, N <= _hip.WASS_MAX_MEMBERS; one
-  value lane; the same stage 2).
+  value lane; the same stage 2) / 'ivl' (interval statistics of an ensemble, wbx_ens_interval_partial: `ens` = {'member_dim', 'M',
+  'fair': False}, `cat` = {'lanes' (a set of _hip.IVL_* bits), 'params': {bit: {'bounds': (q_lo, q_hi), 'threshold', 'q_index':
+  positions of the two levels along the climatology's quantile dim}}, 'quantile_dim'}, inputs (p, t[, climatology]) with the
+  climatology behind `gather` like ACC's; one value lane per bit set, in the order Covered, Confident, JaccardDistant; the same
+  stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;

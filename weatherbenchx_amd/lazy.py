@@ -56,6 +56,9 @@ FUSED_VARIOGRAM = os.environ.get('WBX_FUSED_VARIOGRAM', '1') != '0'
 # False (WBX_FUSED_WASSERSTEIN=0): WassersteinDistance is a pooled float64 sort and two cumulative sums on the host, reduced as before
 # wbx_ens_wasserstein_partial existed (A/B timing, tests).
 FUSED_WASSERSTEIN = os.environ.get('WBX_FUSED_WASSERSTEIN', '1') != '0'
+# False (WBX_FUSED_INTERVALS=0): Covered, Confident and JaccardDistant (Opportunism) take two host quantile fields each, an aligned
+# copy of the climatology and a Boolean array per statistic, reduced as before wbx_ens_interval_partial existed (A/B timing, tests).
+FUSED_INTERVALS = os.environ.get('WBX_FUSED_INTERVALS', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -207,7 +210,8 @@ class FusedGroup:
     self.p, self.t = p, t
     self.ens = ens  # {'member_dim', 'M'}; kind 'enrg': + {'fair' (None: no spread statistic has said yet), 'norm_dims', 'norm_sizes'};
     # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}; kinds 'ens2', 'wass': + {'N'}
-    self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}
+    self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
+    # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -216,11 +220,12 @@ class FusedGroup:
     self.dims, self.sizes, self.coords = _stat_frame([p, t], drop_dims=drop)
     self.cache: dict = {}
 
-  def attach_climatology(self, ref: ClimatologyRef, key) -> bool:
+  def attach_climatology(self, ref: ClimatologyRef, key, own_dims=()) -> bool:
+    """`own_dims`: dims of the climatology that the kernel addresses itself (the quantile dim of the interval statistics)."""
     if self.clim is None:
       # frame check: aligned climatology dims must already be statistic dims (it only broadcasts)
       for d in ref.aligned_dims():
-        if d not in self.dims:
+        if d not in self.dims and d not in own_dims:
           return False
       for d in ref.source.dims:
         if d in self.dims and d in ref.source._coords and d in self.coords:  # pylint: disable=protected-access
@@ -242,6 +247,8 @@ class FusedGroup:
   def inputs_and_func(self):
     if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass'):
       return [self.p, self.t], 0
+    if self.kind == 'ivl':
+      return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
     if self.clim is not None:
       return [self.p, self.t, self.clim.source], _hip.DET6
     return [self.p, self.t], _hip.DET3
@@ -254,6 +261,9 @@ class FusedGroup:
       ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                  skipna=skipna, clim=self.clim, ens=ens)
+    if self.kind == 'ivl':  # one launch for every lane asked for so far, the climatology gathered in place like ACC's
+      return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
+                                 skipna=skipna, clim=self.clim, ens=self.ens, cat=self.cat)
     # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
     # group are its own); 'cat', 'cont': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
@@ -349,6 +359,15 @@ class FusedGroup:
             import torch  # pylint: disable=g-import-not-at-top
             return torch.as_tensor(arr, device=da.data.device)
       return arr
+    if self.kind == 'ivl':  # stage 1 with every dim kept, as for 'wass'; `lane`: the value lane among those launched
+      with engine.synchronous_results():
+        values, _, out_dims = self.reduce((), None, (), use_mask=False, skipna=False)
+      arr = np.asarray(values, np.float64)[lane] != 0
+      arr = np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims]))
+      if xr._is_torch(self.p.data):  # pylint: disable=protected-access  (a Boolean tensor on the payload's device, as the host route gives)
+        import torch  # pylint: disable=g-import-not-at-top
+        return torch.as_tensor(arr, device=self.p.data.device)
+      return arr
     inputs, func = self.inputs_and_func()
     ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
     gather, inputs = _gather_spec(self.clim, inputs, self.dims)
@@ -394,7 +413,7 @@ def _regather(p_new, g):
     return None
 
 
-def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, *, func, mask, skipna, clim, ens):
+def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, *, func, mask, skipna, clim, ens, cat=None):
   gather, inputs = _gather_spec(clim, inputs, dims)
   rec = replay.active() if clim is not None else None
   if rec is not None:  # a chunk that is being recorded: what its gather plans have to be rebuilt from for the next chunk
@@ -402,7 +421,7 @@ def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, 
                           'dtype_code': engine._common_dtype([i.data for i in inputs]), 'regather': _regather}  # pylint: disable=protected-access
   try:
     return engine.reduce_statistics(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
-                                    skipna=skipna, gather=gather, ens=ens)
+                                    skipna=skipna, gather=gather, ens=ens, cat=cat)
   except ValueError as e:
     if clim is None or 'innermost' not in str(e):
       raise
@@ -410,7 +429,7 @@ def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, 
     aligned = clim.aligned_view()
     inputs = list(inputs[:2]) + [aligned]
     return engine.reduce_statistics(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
-                                    skipna=skipna, gather=None, ens=ens)
+                                    skipna=skipna, gather=None, ens=ens, cat=cat)
   finally:
     if rec is not None:
       rec.gather_context = None
@@ -823,6 +842,71 @@ def wasserstein_statistic(p, t, ensemble_dim: str) -> xr.DataArray:
   ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'N': t.sizes[ensemble_dim], 'fair': False}
   grp = _group_for('wass', p, t, ens=ens, clim_key=('wass',))
   return LazyStatistic(grp, 0, name=p.name)
+
+
+class LazyInterval(LazyStatistic):
+  """Covered / Confident / JaccardDistant as a Boolean statistic on a FusedGroup of kind 'ivl'.  Its value lane is its place among
+  the lanes the group launches, which grows while statistics join: it is looked up when asked for, not fixed here."""
+
+  @property
+  def _lane(self) -> int:
+    return bin(int(self._group.cat['lanes']) & (self._bit - 1)).count('1')
+
+  @_lane.setter
+  def _lane(self, bit: int):
+    self._bit = int(bit)
+
+  @property
+  def dtype(self):
+    return np.dtype(bool)
+
+
+IVL_QUANTILE_DIM = 'quantile'  # the climatology's dim of quantile levels (categorical.py: `climatology.sel(quantile=...)`)
+IVL_MAX_GROUPS = 4  # groups of one (p, t, member dim): a statistic whose parameters differ from its kind's in a group opens the next
+
+
+def interval_statistic(p, t, clim_ref: ClimatologyRef | None, ensemble_dim: str, which: str, bounds, threshold=None,
+                       clim_key=None) -> xr.DataArray:
+  """`which` in ('Covered', 'Confident', 'JaccardDistant') of the ensemble `p` -- against `t` (Covered) or the climatology behind
+  `clim_ref` (the other two) -- as a LazyInterval on a FusedGroup of kind 'ivl' (wbx_ens_interval_partial).  `bounds`: the two
+  quantile levels; `threshold`: confidence_threshold / the Jaccard threshold.  The (p, t) objects, the member dim and the
+  climatology key the group, so the three statistics of one Opportunism meet in one group whatever their levels and thresholds,
+  and its first reduction launches every lane that has joined by then.  The two levels of a lane become positions along the
+  climatology's quantile dim (element offsets once its device layout is known); the climatology itself is gathered in place.
+  Raises ValueError / _NeedsAlignment where the launch cannot take the inputs as they stand: the caller keeps the host route."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if ensemble_dim not in p.dims or ensemble_dim in t.dims:
+    raise ValueError(f'{ensemble_dim!r} must be a dim of the predictions and not of the targets')
+  bit = engine.IVL_BITS[which]
+  lane = {'bounds': (float(bounds[0]), float(bounds[1])), 'threshold': None, 'q_index': None}
+  if bit != _hip.IVL_COVERED:
+    if clim_ref is None or IVL_QUANTILE_DIM not in clim_ref.source.dims:
+      raise ValueError(f'{which} needs a climatology with a {IVL_QUANTILE_DIM!r} dim')
+    try:
+      lane['q_index'] = tuple(int(j) for j in clim_ref.source._index_positions(IVL_QUANTILE_DIM, list(lane['bounds'])))  # pylint: disable=protected-access
+    except KeyError as e:
+      raise ValueError(str(e)) from e
+    lane['threshold'] = float(threshold)
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': False}
+  for n in range(IVL_MAX_GROUPS):
+    grp = _group_for('ivl', p, t, ens=ens, clim_key=('ivl', n),
+                     cat={'lanes': 0, 'params': {}, 'quantile_dim': IVL_QUANTILE_DIM})
+    if bit != _hip.IVL_COVERED and not grp.attach_climatology(clim_ref, clim_key, own_dims=(IVL_QUANTILE_DIM,)):
+      if grp.clim is None:  # (not another climatology: this one does not fit the frame)
+        raise ValueError(f'climatology dims {clim_ref.aligned_dims()} do not broadcast against the statistic dims {grp.dims}')
+      continue
+    have = grp.cat['params'].get(bit)
+    if have is None:
+      if grp.cache:  # sums of a launch without this lane: the value lanes move
+        grp.cache.clear()
+      grp.cat['params'][bit] = lane
+      grp.cat['lanes'] |= bit
+    elif have != lane:
+      continue
+    # Confident and JaccardDistant never look at the targets: the predictions' and the climatology's coordinates only
+    names = None if bit == _hip.IVL_COVERED else frozenset(p._coords) | frozenset(clim_ref._coords)  # pylint: disable=protected-access
+    return LazyInterval(grp, bit, name=p.name, coord_names=names)
+  raise ValueError(f'more than {IVL_MAX_GROUPS} interval groups of one (predictions, targets) pair')
 
 
 ENS2_LANE = {'CRPSSkill': 0, 'UnbiasedEnsembleMeanSquaredError': 1}

@@ -6,7 +6,9 @@ statistic), and every score below is a formula on those four means.  Inputs come
 `ContinuousToBins` (thresholded fields, probability bins).
 
 SEEPS and the interval statistics (Confident / Covered / JaccardDistant -> Opportunism) follow the same pattern with a
-climatology beside the chunk.
+climatology beside the chunk.  The Aggregator gets the sums of the three interval statistics of one (predictions, targets,
+climatology) from one launch of wbx_ens_interval_partial (lazy.interval_statistic), which sorts a point's members once; the per-point
+values anybody reads are Boolean as before.
 """
 from __future__ import annotations
 
@@ -14,6 +16,8 @@ from typing import Hashable, Mapping, Sequence, Union
 
 import numpy as np
 
+from weatherbenchx_amd import _hip
+from weatherbenchx_amd import engine
 from weatherbenchx_amd import lazy
 from weatherbenchx_amd import xarray_lite as xr
 from weatherbenchx_amd.metrics import base
@@ -232,9 +236,65 @@ def _ensemble_quantile(da: xr.DataArray, q: float, dim: str) -> xr.DataArray:
   return wrappers.EnsembleQuantiles(which='both', quantiles=[q], ensemble_dim=dim, quantile_dim='_q').transform_fn(da).isel(_q=0, drop=True)
 
 
+def _fused_interval(which: str, predictions, targets, climatology, ensemble_dim: str, bounds, threshold=None):
+  """Covered / Confident / JaccardDistant as a lazy statistic that the Aggregator reduces with wbx_ens_interval_partial
+  (lazy.interval_statistic), or None where the host route has to do it: the switch is off, no device or library, or no such symbol
+  in it, a dtype other than float32 / float64 or dtypes of predictions, targets and climatology that differ, an ensemble of fewer
+  than 1 or more than _hip.IVL_MAX_MEMBERS members, a climatology that is no index table or lacks one of the two quantile labels, a
+  `mask` coordinate along the member dim, nothing left of the frame without the member dim, frames that need broadcasting or
+  joining (a dim one input lacks, sizes or labels that differ, a climatology dim the statistic does not have), and a result whose
+  dims, coordinates or name would differ from the host route's.  No shape class is kept from the kernel for speed: it won at every
+  shape that was measured."""
+  if not lazy.FUSED_INTERVALS:
+    return None
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  e = ensemble_dim
+  if e not in p.dims or e in t.dims:
+    return None
+  dtype = str(p.dtype)
+  if dtype not in ('float32', 'float64') or str(t.dtype) != dtype:
+    return None
+  clim = climatology if isinstance(climatology, lazy.ClimatologyRef) else None
+  if which != 'Covered' and (clim is None or str(clim.dtype) != dtype):
+    return None
+  if not 1 <= p.sizes[e] <= _hip.IVL_MAX_MEMBERS:
+    return None
+  frame = tuple(d for d in p.dims if d != e)
+  if not frame or set(frame) != set(t.dims):
+    return None
+  if 'mask' in p.coords and e in p.coords['mask'].dims:
+    return None
+  if which == 'Covered' and t.name is not None and t.name != p.name:  # (the host route's comparison drops the name)
+    return None
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+    return None
+  if not engine.ens_interval_available(ctx):
+    return None
+  try:
+    key = None if clim is None else (id(clim.source.data), clim.source.__dict__.get('_mutations', 0))
+    stat = lazy.interval_statistic(p, t, clim, e, which, bounds, threshold, clim_key=key)
+    # what the host route's comparison carries: the frame and the coordinates of (quantiles of p, t) or of (quantiles of p,
+    # climatology without its quantile dim)
+    other, drop = (t, (e,)) if which == 'Covered' else (clim, (e, lazy.IVL_QUANTILE_DIM))
+    want_dims, _, want_coords = lazy._stat_frame_walk([p, other], drop_dims=drop)  # pylint: disable=protected-access
+  except (lazy._NeedsAlignment, ValueError):  # pylint: disable=protected-access  (the host route broadcasts, or says what is wrong)
+    return None
+  if stat.dims != want_dims or set(stat._coords) != set(want_coords):  # pylint: disable=protected-access
+    return None
+  return stat
+
+
 class Covered(base.PerVariableStatistic):
   """Whether the target lies inside the ensemble's [low, high] quantile interval (linear-interpolated quantiles, both ends
-  included).  categorical.py:750-785."""
+  included).  categorical.py:750-785.
+
+  Under the Aggregator the indicator is summed by wbx_ens_interval_partial, which sorts the members in their own type and
+  interpolates in float64 in NumPy's order of operations.  For float64 payloads that is the host route's indicator, point by point.
+  For float32 payloads the host route interpolates in float32 (and NumPy and torch do not agree with each other there), so an
+  indicator can differ where the target lies within a float32 rounding of a quantile -- and, for Confident, where the scaled
+  climatological spread lies that close to the ensemble's."""
 
   def __init__(self, ensemble_dim: str, interval_quantile_boundaries: tuple = (0.1, 0.9)):
     self._ensemble_dim = ensemble_dim
@@ -245,6 +305,11 @@ class Covered(base.PerVariableStatistic):
     return f'Covered_interval_low={self._interval_low}_interval_high={self._interval_high}'
 
   def _compute_per_variable(self, predictions, targets):
+    fused = _fused_interval('Covered', predictions, targets, None, self._ensemble_dim, (self._interval_low, self._interval_high))
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
+    """The indicator from two quantile fields of the ensemble, on whatever holds the payload."""
     low = _ensemble_quantile(predictions, self._interval_low, self._ensemble_dim)
     high = _ensemble_quantile(predictions, self._interval_high, self._ensemble_dim)
     return (low <= targets) & (targets <= high)
@@ -272,6 +337,12 @@ class Confident(base.PerVariableStatisticWithClimatology):
     return f'Confident_conf_thres={self._confidence_threshold}_spread_low={self._spread_low}_spread_high={self._spread_high}'
 
   def _compute_per_variable_with_aligned_climatology(self, predictions, targets, aligned_climatology):
+    fused = _fused_interval('Confident', predictions, targets, aligned_climatology, self._ensemble_dim,
+                            (self._spread_low, self._spread_high), self._confidence_threshold)
+    return fused if fused is not None else self.host_per_variable(predictions, targets, aligned_climatology)
+
+  def host_per_variable(self, predictions, targets, aligned_climatology):
+    """The indicator from two quantile fields of the ensemble and an aligned copy of the climatology."""
     del targets
     clim = _aligned(aligned_climatology)
     spread = (_ensemble_quantile(predictions, self._spread_high, self._ensemble_dim)
@@ -295,6 +366,12 @@ class JaccardDistant(base.PerVariableStatisticWithClimatology):
     return f'JaccardDistant_threshold={self._threshold}_interval_low={self._interval_low}_interval_high={self._interval_high}'
 
   def _compute_per_variable_with_aligned_climatology(self, predictions, targets, aligned_climatology):
+    fused = _fused_interval('JaccardDistant', predictions, targets, aligned_climatology, self._ensemble_dim,
+                            (self._interval_low, self._interval_high), self._threshold)
+    return fused if fused is not None else self.host_per_variable(predictions, targets, aligned_climatology)
+
+  def host_per_variable(self, predictions, targets, aligned_climatology):
+    """The indicator from two quantile fields of the ensemble and an aligned copy of the climatology."""
     del targets
     clim = _aligned(aligned_climatology)
     a_lo = _ensemble_quantile(predictions, self._interval_low, self._ensemble_dim)
