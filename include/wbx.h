@@ -545,6 +545,44 @@ int wbx_ens_interval_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /*
                              int lanes /* WBX_IVL_* bit set */, const wbx_ivl_lane* params /* HOST, three entries */, const void* p,
                              const void* t, const void* c, const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: contingency tables of ensemble event probabilities (joined ABI 13) -----------------------------------
+ * The four cells TruePositives / FalsePositives / FalseNegatives / TrueNegatives (categorical.py:25-101) behind the documented chain
+ * ContinuousToBinary('both', event thresholds) -> EnsembleMean('predictions') -> ContinuousToBinary('predictions', probability
+ * thresholds) or ContinuousToBins('predictions', probability edges) (wrappers.py; RelativeEconomicValue and Reliability end in it),
+ * in one pass over p and t: no [nthr][M][frame] indicator array, no [nthr][nslot][frame] arrays are formed.  p has a member axis of
+ * length M and element stride `member_stride` that is not part of key / depth / x, as for wbx_ens_partial.
+ * Counts and observation.  Per point, with members x_m, target y and event thresholds a_k = thresholds[k]:
+ *     c_k = #{m : (double)x_m > a_k} in 0..M,   o_k = [(double)y > a_k]        (strict, on the threshold as given)
+ * A comparison with a NaN event threshold is false; -0.0 > 0.0 is false; +-inf compare as IEEE says.  float32 inputs are compared
+ * in float32 against the threshold rounded toward -inf to float32, which decides exactly like the float64 comparison for every
+ * float32 value (+-inf and thresholds beyond the float32 range included; rounding to nearest would not: float(0.1) > 0.1).
+ * Prediction per slot.  The member mean of the 0 / 1 indicators is a function of c_k alone, and so is whether it falls into
+ * probability slot j; the caller hands every slot over as a run of counts: P_kj = (lo_j <= c_k && c_k <= hi_j), `slots` a DEVICE
+ * int32[2 * nslot] of (lo, hi) pairs, lo > hi an empty slot.  The kernel never sees a probability.
+ *     TP = P_kj & o_k,  FP = P_kj & !o_k,  FN = !P_kj & o_k,  TN = !P_kj & !o_k  -- exactly one of them is 1
+ * Lane order is part of the ABI: 4 * nthr * nslot value lanes, cell * (nthr * nslot) + k * nslot + j, cell in (TP, FP, FN, TN).
+ * Count lanes follow the library's convention (none / one shared / one per value lane); under SKIPNA all of them are equal (the
+ * number of valid, non-NaN points).  partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial: wbx_s1_partial_len with
+ * lanes = 4 * nthr * nslot; wbx_contract, wbx_contract_bits, the accumulators and the chunk records take it unchanged.
+ * Per partial the integer counts #(P & O) and #P per (k, j), #O per k and the numbers of good (valid, non-NaN) and of valid points
+ * are held, and the cells are formed once: FP = #P - TP, FN = #O - TP, TN = N - #P - #O + TP.  No floating-point number is added and
+ * nothing is added atomically: every output is an integer < 2^32 held in fp64 (or NaN), a function of the inputs and the plan only.
+ * A point with a NaN member or a NaN target is a NaN statistic in all lanes: without flags it poisons every value lane of its
+ * partial; under WBX_FLAG_MASKED alone it contributes exactly 0 where the mask is 0 and poisons where it is not; under
+ * WBX_FLAG_SKIPNA it is counted out -- exactly as in wbx_contingency_partial.
+ * Refused (WBX_ERR_INVALID, output untouched): nthr < 1, nslot < 1 or nthr * nslot > WBX_EPC_MAX_PAIRS, M outside
+ * 1..WBX_EPC_MAX_MEMBERS, an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, plane_rows != 0 or
+ * x_weights, and depth_chunk * nx >= 2^32 (the counters are uint32).  vec = 4 is accepted and read with dword loads (a lane owns a
+ * point and walks its members: the wave's load of one member row is coalesced as it is).  nkey == 0 touches nothing; ndepth == 0
+ * or nx == 0 zero the partial. */
+#define WBX_EPC_CELLS 4        /* TP, FP, FN, TN */
+#define WBX_EPC_MAX_PAIRS 16   /* nthr * nslot per launch */
+#define WBX_EPC_MAX_MEMBERS 256
+int wbx_ens_prob_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M,
+                                     int64_t member_stride, int nthr, const double* thresholds /* DEVICE float64[nthr] */, int nslot,
+                                     const int32_t* slots /* DEVICE int32[2 * nslot]: lo, hi */, const void* p, const void* t,
+                                     const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -765,7 +803,8 @@ typedef enum wbx_fn {
   WBX_FN_ZONAL_SPECTRUM_SLABS = 11, WBX_FN_DET_SPECTRUM = 12, WBX_FN_DET_SPECTRUM_SLABS = 13, WBX_FN_ACC_ADD = 14,
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
-  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25
+  WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
+  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

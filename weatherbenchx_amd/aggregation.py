@@ -319,7 +319,7 @@ class Aggregator:
     reduce_set = set(self.reduce_dims)
     if not reduce_set <= set(stat.dims):
       return None  # variables without every reduce dim are dropped (aggregation.py:305-309)
-    if isinstance(stat, lazy.LazyContingency) and stat.is_lazy:
+    if isinstance(stat, (lazy.LazyContingency, lazy.LazyEnsProbContingency)) and stat.is_lazy:
       fused = self._try_contingency(stat, reduce_set, use_mask, skipna)
       if fused is not None:
         return fused  # (else: `.data` is read below -- the host route)
@@ -525,15 +525,19 @@ class Aggregator:
                           attrs=stat.attrs, _raw_coords=True)
     return AggregationState(mk(values), mk(counts))
 
-  def _try_contingency(self, stat: 'lazy.LazyContingency', reduce_set, use_mask, skipna):
-    """The fused route for a cell of a thresholded contingency table, or None for the host route.  Taken when the launch context
+  def _try_contingency(self, stat, reduce_set, use_mask, skipna):
+    """The fused route for a cell of a thresholded contingency table (lazy.LazyContingency: one threshold dim) or of the tables of
+    an ensemble's event probabilities (lazy.LazyEnsProbContingency: an event dim and a slot dim), or None for the host route.  What
+    is said of the threshold dim below holds for each of the statistic's `lane_dims`.  Taken when the launch context
     can make the call (engine.contingency_available: any other context object -- the NumPy plan interpreter has no library --
     keeps the host route), the threshold dim is not reduced, and W does not involve it.  W is built on the statistic's frame
     WITHOUT the threshold dim (plugins such as LatitudeBins broadcast their masks to whatever dims the statistic has): right for
     this package's own weightings and binnings, which look at coordinates only; a plugin from elsewhere may look at the values,
     and one that asks for the threshold coordinate does not find it -- both keep the host route."""
-    thr_dim = stat._threshold_dim  # pylint: disable=protected-access
-    if not lazy.FUSED_CONTINGENCY or thr_dim in reduce_set or not engine.contingency_available(_hip.default_context()):
+    lane_dims = set(stat.lane_dims)
+    if lane_dims & reduce_set:
+      return None
+    if not stat.launchable():
       return None
     own = (binning.__name__, weighting.__name__)
     if not all(type(m).__module__ in own for m in tuple(self.weigh_by or ()) + tuple(self.bin_by or ())):
@@ -558,25 +562,28 @@ class Aggregator:
     if wp is None:
       return None
     w_da, bin_dims = wp
-    if thr_dim in bin_dims or (w_da is not None and thr_dim in w_da.dims):
+    if lane_dims & set(bin_dims) or (w_da is not None and lane_dims & set(w_da.dims)):
       return None
     return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
 
-  def _reduce_contingency(self, stat: 'lazy.LazyContingency', w_da, bin_dims, use_mask, skipna):
+  def _reduce_contingency(self, stat, w_da, bin_dims, use_mask, skipna):
     """One cell of a thresholded contingency table: the four cells of a (p, t) pair are the lane blocks of ONE launch
-    (wbx_contingency_partial), run by whichever cell comes first and kept on the group; this cell takes its block
-    values[cell * K:(cell + 1) * K] as a view, the thresholds come back as the statistic's trailing dimension."""
+    (wbx_contingency_partial; wbx_ens_prob_contingency_partial, one per block of pairs), run by whichever cell comes first and kept
+    on the group; this cell takes its block values[cell * K:(cell + 1) * K] as a view (K: the product of the statistic's
+    `lane_shape`), the thresholds come back as the statistic's trailing dimension(s)."""
     grp = stat._group  # pylint: disable=protected-access
-    thr_dim = stat._threshold_dim  # pylint: disable=protected-access
+    lane_dims, lane_shape = tuple(stat.lane_dims), tuple(stat.lane_shape)
     key = self._cache_key(w_da, bin_dims, use_mask, skipna, ('cont',))
     hit = grp.cache.get(key)
     if hit is None:
       hit = grp.cache[key] = grp.reduce(self.reduce_dims, w_da, bin_dims, use_mask=use_mask, skipna=skipna)
     values, counts, out_dims = hit
-    k, cell = stat.nthr, stat._cell  # pylint: disable=protected-access
+    k, cell = int(np.prod(lane_shape, dtype=np.int64)), stat._cell  # pylint: disable=protected-access
     values, counts = values[cell * k:(cell + 1) * k], counts[cell * k:(cell + 1) * k]
-    dims_in = (thr_dim,) + tuple(out_dims)
-    final_dims = tuple(d for d in tuple(grp.dims) + (thr_dim,) if d in dims_in) + tuple(bin_dims)
+    if len(lane_shape) > 1:  # (an axis split into the dims it stands for: still a view)
+      values, counts = values.reshape(lane_shape + values.shape[1:]), counts.reshape(lane_shape + counts.shape[1:])
+    dims_in = lane_dims + tuple(out_dims)
+    final_dims = tuple(d for d in tuple(grp.dims) + lane_dims if d in dims_in) + tuple(bin_dims)
     # (exactly the host route's coordinates: every one whose dims all survive stays, a `mask` among them -- see _aggregate)
     coords = {n: x for n, x in stat._coords.items() if set(x[0]) <= set(final_dims)}  # pylint: disable=protected-access
     if w_da is not None:

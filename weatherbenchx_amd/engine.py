@@ -435,6 +435,18 @@ def _threshold_table(ctx, thresholds):
   return thr
 
 
+def _slot_table(ctx, slots):
+  """The device copy of an int32 table of (lo, hi) count runs (wbx_ens_prob_contingency_partial), uploaded once per (device, contents)."""
+  slots = np.ascontiguousarray(slots, np.int32)
+  tkey = (ctx.device_id, 'i32', slots.tobytes())
+  buf = _thr_cache.get(tkey)
+  if buf is None:
+    if len(_thr_cache) > 64:
+      _thr_cache.clear()
+    buf = _thr_cache[tkey] = ctx.upload(slots)
+  return buf
+
+
 def contingency_available(ctx) -> bool:
   """Whether `ctx` can launch wbx_contingency_partial: a real library context whose library exports the entry point.  Any
   other context object (the NumPy plan interpreter of the CPU tests has no library) keeps the host route."""
@@ -492,6 +504,16 @@ def ens_interval_available(ctx) -> bool:
     return False
   try:
     return getattr(ctx.lib, 'wbx_ens_interval_partial', None) is not None
+  except AttributeError:
+    return False
+
+
+def ens_prob_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_prob_contingency_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_prob_contingency_partial', None) is not None
   except AttributeError:
     return False
 
@@ -773,6 +795,7 @@ Ens2Args = collections.namedtuple('Ens2Args', 'm mstride n_t tstride')
 CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  # thr: a table; None with cstride: a field (input 2)
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
+EpcArgs = collections.namedtuple('EpcArgs', 'nthr thr nslot slots')
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
 VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
@@ -804,6 +827,18 @@ def _erps_operands(ctx, devs, func, ens, cat, mdim):
     raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
   return 1, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), RpsArgs(
       nthr, _threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
+
+
+def _epc_operands(ctx, devs, func, ens, cat, mdim):
+  thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
+  slots = np.asarray(cat['slots'], np.int32).reshape(-1, 2)
+  nthr, nslot = int(thr.size), int(slots.shape[0])
+  if nthr < 1 or nslot < 1 or nthr * nslot > _hip.EPC_MAX_PAIRS:
+    raise ValueError(f'one launch takes 1..{_hip.EPC_MAX_PAIRS} (event threshold, probability slot) pairs (got {nthr} x {nslot})')
+  if not 1 <= int(ens['M']) <= _hip.EPC_MAX_MEMBERS:
+    raise ValueError(f"one launch takes 1..{_hip.EPC_MAX_MEMBERS} members (got {ens['M']})")
+  return _hip.EPC_CELLS * nthr * nslot, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), EpcArgs(
+      nthr, _threshold_table(ctx, thr), nslot, _slot_table(ctx, slots))
 
 
 def norm_run(layout, dims, sizes):
@@ -914,6 +949,10 @@ _KINDS = {
                   lambda d, out, dt, func, ens, cat:
                   ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
                                            int(bool(cat.right)), d[0], d[1], d[3], out))),
+    'epc': _Kind(_epc_operands, ('thr', 'slots'),
+                 lambda d, out, dt, func, ens, cat:
+                 ('wbx_ens_prob_contingency_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), int(cat.nslot),
+                                                       _table_ptr(cat.slots), d[0], d[1], d[3], out))),
     'enrg': _Kind(_enrg_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
     'vgrm': _Kind(_vgrm_operands, (),
@@ -1640,7 +1679,10 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   'fair': False}, `cat` = {'lanes' (a set of _hip.IVL_* bits), 'params': {bit: {'bounds': (q_lo, q_hi), 'threshold', 'q_index':
   positions of the two levels along the climatology's quantile dim}}, 'quantile_dim'}, inputs (p, t[, climatology]) with the
   climatology behind `gather` like ACC's; one value lane per bit set, in the order Covered, Confident, JaccardDistant; the same
-  stage 2).
+  stage 2) / 'epc' (contingency tables of ensemble event probabilities, wbx_ens_prob_contingency_partial: the operands of 'erps' --
+  `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag)} --, `cat` = {'thresholds': float64 ndarray of K event
+  thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts}, K * J <= _hip.EPC_MAX_PAIRS; value lane
+  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;

@@ -59,6 +59,11 @@ FUSED_WASSERSTEIN = os.environ.get('WBX_FUSED_WASSERSTEIN', '1') != '0'
 # False (WBX_FUSED_INTERVALS=0): Covered, Confident and JaccardDistant (Opportunism) take two host quantile fields each, an aligned
 # copy of the climatology and a Boolean array per statistic, reduced as before wbx_ens_interval_partial existed (A/B timing, tests).
 FUSED_INTERVALS = os.environ.get('WBX_FUSED_INTERVALS', '1') != '0'
+# False (WBX_FUSED_ENS_PROB=0): contingency tables of ensemble event probabilities (TruePositives .. behind ContinuousToBinary('both')
+# -> EnsembleMean('predictions') -> ContinuousToBinary / ContinuousToBins('predictions'): RelativeEconomicValue, Reliability) build
+# the [K, M, frame] and [K, J, frame] indicator arrays on the host and reduce them as before wbx_ens_prob_contingency_partial existed
+# (A/B timing, tests).
+FUSED_ENS_PROB = os.environ.get('WBX_FUSED_ENS_PROB', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -245,7 +250,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc'):
       return [self.p, self.t], 0
     if self.kind == 'ivl':
       return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
@@ -265,11 +270,13 @@ class FusedGroup:
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                  skipna=skipna, clim=self.clim, ens=self.ens, cat=self.cat)
     # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
-    # group are its own); 'cat', 'cont': one per block
+    # group are its own); 'cat', 'cont', 'epc': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
                                                   skipna=skipna, ens=self.ens, cat=cat)
     if self.kind == 'cat':
       return self._reduce_cat(launch, mask, skipna)
+    if self.kind == 'epc':
+      return self._reduce_epc(launch)
     return self._reduce_cont(launch) if self.kind == 'cont' else launch(self.cat)
 
   def _reduce_cat(self, launch, mask, skipna):
@@ -300,6 +307,28 @@ class FusedGroup:
     return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block])} for k0 in range(0, nthr, block)], launch,
                              lambda parts: np.concatenate([cells(a) for a in parts], axis=1).reshape(
                                  (_hip.CONT_CELLS * nthr,) + parts[0].shape[1:]))
+
+  def _reduce_epc(self, launch):
+    """Contingency tables of ensemble event probabilities: one launch for up to _hip.EPC_MAX_PAIRS (event threshold k, probability
+    slot j) pairs; more are cut into blocks -- pairs are independent of one another --, along j first and, where the thresholds
+    alone are more than a launch holds, along k too, one launch each, joined on the host cell by cell: the result is (4 * K * J,) +
+    out_dims with lane cell * (K * J) + k * J + j whatever the number of launches."""
+    thr = np.asarray(self.cat['thresholds'], np.float64).reshape(-1)
+    slots = np.asarray(self.cat['slots'], np.int32).reshape(-1, 2)
+    nthr, nslot, block = int(thr.size), int(slots.shape[0]), _hip.EPC_MAX_PAIRS
+    if nthr * nslot <= block:
+      return launch({'thresholds': thr, 'slots': slots})
+    bk = min(nthr, block)
+    bj = max(1, block // bk)
+    cuts = [(k0, min(k0 + bk, nthr), j0, min(j0 + bj, nslot)) for k0 in range(0, nthr, bk) for j0 in range(0, nslot, bj)]
+    subs = [{'thresholds': np.ascontiguousarray(thr[k0:k1]), 'slots': np.ascontiguousarray(slots[j0:j1])} for k0, k1, j0, j1 in cuts]
+
+    def join(parts):
+      out = np.empty((_hip.EPC_CELLS, nthr, nslot) + parts[0].shape[1:], np.float64)
+      for (k0, k1, j0, j1), a in zip(cuts, parts):  # (the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from)
+        out[:, k0:k1, j0:j1] = a.reshape((_hip.EPC_CELLS, k1 - k0, j1 - j0) + a.shape[1:])
+      return out.reshape((_hip.EPC_CELLS * nthr * nslot,) + parts[0].shape[1:])
+    return _reduce_in_blocks(subs, launch, join)
 
   def _cat_blocks(self, block: int):
     """self.cat cut into runs of at most `block` categories (kept: a block's threshold table / field is uploaded once)."""
@@ -703,6 +732,19 @@ class LazyContingency(xr.LazyPickleMixin, xr.DataArray):
   def nthr(self) -> int:
     return int(np.asarray(self._group.cat['thresholds']).size)
 
+  # what the Aggregator's route for the four cells asks (shared with LazyEnsProbContingency)
+  @property
+  def lane_dims(self) -> tuple:
+    return (self._threshold_dim,)
+
+  @property
+  def lane_shape(self) -> tuple:
+    return (self.nthr,)
+
+  @staticmethod
+  def launchable() -> bool:
+    return FUSED_CONTINGENCY and engine.contingency_available(_hip.default_context())
+
   def frame(self) -> xr.DataArray:
     """The statistic's frame without the threshold dim -- dims, sizes, coordinates (the mask among them), a payload of zeros that
     takes no memory: what coordinate-only weightings and binnings are asked for their W with (one object per group)."""
@@ -749,6 +791,152 @@ def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr
   cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim}
   grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
   return LazyContingency(grp, cell, threshold_dim, name=p.name)
+
+
+EPC_COUNT_DIM = '__member_count__'  # the dim of the column of counts c = 0..M that the slot table is derived from
+
+
+def ens_prob_slot_table(mean_transform, inner_transform, m: int, ensemble_dim: str, slot_dim: str, like=None):
+  """Which member counts c = 0..M put a point into probability slot j, read off the host route itself: `mean_transform`
+  (wrappers.EnsembleMean) and then `inner_transform` (ContinuousToBinary / ContinuousToBins on the predictions) applied to a column
+  [M, M + 1] of float32 members with c ones among them, and `!= 0` of what comes out (what categorical._indicator reads).  ->
+  (slots int32 [J, 2] of runs lo <= c <= hi, lo > hi: an empty slot; the coordinates {name: (dims, values)} the inner transform puts
+  on `slot_dim`), or None where a slot's counts are not one contiguous run or the result is not ('count', slot_dim).  `like`: a
+  payload (NumPy array or tensor) whose kind and device the column takes."""
+  # (kept per contents: the four cells of every variable and chunk ask for the same table)
+  values = getattr(inner_transform, '_threshold_value', getattr(inner_transform, '_bin_values', None))
+  torch_like = like is not None and xr._is_torch(like)  # pylint: disable=protected-access
+  key = None
+  if isinstance(values, (list, tuple, np.ndarray)):
+    try:
+      key = (type(inner_transform).__name__, slot_dim, str(np.asarray(values).dtype), np.asarray(values, np.float64).tobytes(), bool(getattr(inner_transform, '_enforce_monotonicity', False)),
+             int(m), ensemble_dim, bool(getattr(mean_transform, '_skipna', False)), str(like.device) if torch_like else None)
+    except (TypeError, ValueError):
+      key = None
+  if key is not None and key in _slot_tables:
+    slots, coords = _slot_tables[key]
+    return slots.copy(), dict(coords)
+  out = _derive_slot_table(mean_transform, inner_transform, m, ensemble_dim, slot_dim, like if torch_like else None)
+  if key is not None and out is not None:
+    if len(_slot_tables) > 64:
+      _slot_tables.clear()
+    _slot_tables[key] = (out[0].copy(), dict(out[1]))
+  return out
+
+
+_slot_tables: dict = {}
+
+
+def _derive_slot_table(mean_transform, inner_transform, m, ensemble_dim, slot_dim, like):
+  col = (np.arange(m)[:, None] < np.arange(m + 1)[None, :]).astype(np.float32)
+  if like is not None and xr._is_torch(like):  # pylint: disable=protected-access
+    import torch  # pylint: disable=g-import-not-at-top
+    col = torch.as_tensor(col, device=like.device)
+  da = xr.DataArray(col, dims=(ensemble_dim, EPC_COUNT_DIM))
+  out = xr.as_dataarray(inner_transform.transform_fn(mean_transform.transform_fn(da)))
+  if set(out.dims) != {EPC_COUNT_DIM, slot_dim}:
+    return None
+  hit = (out != 0).transpose(EPC_COUNT_DIM, slot_dim).values
+  hit = np.asarray(hit.cpu() if xr._is_torch(hit) else hit, bool)  # pylint: disable=protected-access
+  slots = np.empty((hit.shape[1], 2), np.int32)
+  for j in range(hit.shape[1]):
+    c = np.flatnonzero(hit[:, j])
+    if c.size == 0:
+      slots[j] = (1, 0)
+    elif int(c[-1]) - int(c[0]) + 1 != c.size:  # (no bin between two edges and no threshold gives this: for transforms to come)
+      return None
+    else:
+      slots[j] = (c[0], c[-1])
+  coords = {k: (tuple(v[0]), np.asarray(v[1])) for k, v in out._coords.items() if set(v[0]) == {slot_dim}}  # pylint: disable=protected-access
+  return slots, coords
+
+
+class LazyEnsProbContingency(xr.LazyPickleMixin, xr.DataArray):
+  """One cell (TruePositives / FalsePositives / FalseNegatives / TrueNegatives) of the contingency tables of an ensemble's event
+  probabilities along two new trailing dims, (event_dim, slot_dim): what `_Indicator` is behind ContinuousToBinary('both', event
+  thresholds) -> EnsembleMean('predictions') -> ContinuousToBinary / ContinuousToBins('predictions').  The four cells of one (p, t)
+  pair, threshold list and inner transform share a FusedGroup of kind 'epc', so the Aggregator gets all of them from one launch per
+  block of pairs (wbx_ens_prob_contingency_partial).  Reading `.data` runs the three transforms and the float32 indicator arithmetic
+  on the host exactly as the unfused route does, and needs no device."""
+
+  def __init__(self, group: FusedGroup, cell: int, name=None):
+    cat = group.cat
+    self._data = None
+    self._event_dim, self._slot_dim = cat['event_dim'], cat['slot_dim']
+    self._dims = tuple(group.dims) + (self._event_dim, self._slot_dim)
+    self.name = name
+    self.attrs = {}
+    self._coords = dict(group.coords)
+    self._coords[self._event_dim] = ((self._event_dim,), np.asarray(cat['event_coord']))
+    self._coords.update(cat['slot_coords'])
+    self._group = group
+    self._cell = int(cell)
+
+  @property
+  def is_lazy(self) -> bool:
+    return self._data is None
+
+  @property
+  def lane_dims(self) -> tuple:
+    return (self._event_dim, self._slot_dim)
+
+  @property
+  def lane_shape(self) -> tuple:
+    cat = self._group.cat
+    return (int(np.asarray(cat['thresholds']).size), int(np.asarray(cat['slots']).shape[0]))
+
+  @staticmethod
+  def launchable() -> bool:
+    return FUSED_ENS_PROB and engine.ens_prob_available(_hip.default_context())
+
+  frame = LazyContingency.frame
+
+  @property
+  def data(self):
+    if self._data is None:
+      from weatherbenchx_amd.metrics import categorical  # pylint: disable=g-import-not-at-top
+      grp = self._group
+      outer, mean, inner = grp.cat['transforms']
+      pb = inner.transform_fn(mean.transform_fn(outer.transform_fn(grp.p)))
+      tb = outer.transform_fn(grp.t)
+      predicted, observed = ((True, True), (True, False), (False, True), (False, False))[self._cell]
+      out = categorical._indicator(pb, tb, predicted, observed)  # pylint: disable=protected-access
+      self._data = out.transpose(*self._dims).data
+    return self._data
+
+  @property
+  def shape(self):
+    return tuple(self._group.sizes[d] for d in self._group.dims) + self.lane_shape
+
+  @property
+  def dtype(self):
+    return np.dtype(np.float32)
+
+
+def ens_prob_contingency_statistic(cell: int, p, t, ensemble_dim: str, event_dim: str, event_values, slot_dim: str, slot_coords, slots,
+                                   transforms, inner_key=None) -> xr.DataArray:
+  """Cell `cell` (0..3: TP, FP, FN, TN) of the tables of (the member count over event threshold k lies in slot j, t > threshold k) as
+  a LazyEnsProbContingency.  `event_values`: the plain sequence of real numbers the outer ContinuousToBinary was built with;
+  `slots`, `slot_coords`: ens_prob_slot_table of the inner transform; `transforms`: (outer, mean, inner), what `.data` runs.  The
+  (p, t) objects, the member dim, the bytes of the event thresholds and the inner transform (`inner_key` and its table) key the
+  group, so the four cells of a pair meet in one group."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if ensemble_dim not in p.dims or ensemble_dim in t.dims:
+    raise ValueError(f'{ensemble_dim!r} must be a dim of the predictions and not of the targets')
+  for d in (event_dim, slot_dim):
+    if d in p.dims or d in t.dims:
+      raise ValueError(f'{d!r} is already a dimension of the inputs')
+  values = list(event_values)
+  thr = np.asarray(values, np.float64).reshape(-1)
+  slots = np.ascontiguousarray(slots, np.int32).reshape(-1, 2)
+  ckey = ('epc', event_dim, thr.tobytes(), slot_dim, inner_key, slots.tobytes())
+  if not _group_known(p, t, 'epc', lambda k: k[3] == ensemble_dim and k[4] == ckey):
+    p, t = _aligned(p, t)
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': False}
+  cat = {'thresholds': thr, 'slots': slots, 'event_dim': event_dim, 'slot_dim': slot_dim, 'event_coord': np.asarray(values),
+         'slot_coords': dict(slot_coords), 'transforms': tuple(transforms)}
+  grp = _group_for('epc', p, t, ens=ens, clim_key=ckey, cat=cat)
+  return LazyEnsProbContingency(grp, cell, name=p.name)
 
 
 def ens_rps_statistic(p, t, ensemble_dim: str, p_thr, t_thr, fair: bool, right_inclusive: bool, bin_dim: str = 'bin') -> xr.DataArray:

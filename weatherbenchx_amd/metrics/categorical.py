@@ -68,6 +68,64 @@ class _Indicator(base.PerVariableStatistic):
       pairs[name] = (p, t)
     return {name: lazy.contingency_statistic(_CELL_INDEX[type(self)], p, t, dim, values) for name, (p, t) in pairs.items()}
 
+  def compute_with_chain(self, transforms, predictions, targets):
+    """This cell behind the documented chain for ensembles as probability forecasts, `transforms` = (ContinuousToBinary('both',
+    [event thresholds], dim_e), EnsembleMean('predictions', ensemble_dim), ContinuousToBinary('predictions', [probability
+    thresholds], dim_p) or ContinuousToBins('predictions', [edges], dim_p)), outermost first, as lazy statistics on the continuous
+    inputs (one fused launch per block of (threshold, slot) pairs for the four cells of a variable,
+    lazy.ens_prob_contingency_statistic), or None: the caller then transforms and computes as usual.  None for any other chain,
+    EnsembleMean(skipna=True) or another `which` on any of the three, labelled thresholds or edges, NaN bin edges, a slot whose
+    member counts are not one run (non-monotone edges), an ensemble dim on the targets or none on the predictions, a threshold dim
+    already on an input, target dims that are not a subset of the prediction dims, dtypes other than float32 / float64, more than
+    _hip.EPC_MAX_MEMBERS members, no device, no entry point, the switch off.  The gate never raises: where the host route would,
+    it does."""
+    if not lazy.FUSED_ENS_PROB or type(self) not in _CELL_INDEX or len(transforms) != 3:  # pylint: disable=unidiomatic-typecheck
+      return None
+    outer, mean, inner = transforms
+    if (type(outer) is not wrappers.ContinuousToBinary or type(mean) is not wrappers.EnsembleMean  # pylint: disable=unidiomatic-typecheck
+        or type(inner) not in (wrappers.ContinuousToBinary, wrappers.ContinuousToBins)):
+      return None
+    if outer.which != 'both' or mean.which != 'predictions' or inner.which != 'predictions' or mean._skipna:  # pylint: disable=protected-access
+      return None
+    values = wrappers.plain_thresholds(outer._threshold_value)  # pylint: disable=protected-access
+    event_dim, e = outer._threshold_dim, mean._ensemble_dim  # pylint: disable=protected-access
+    if type(inner) is wrappers.ContinuousToBinary:  # pylint: disable=unidiomatic-typecheck
+      inner_values, slot_dim = wrappers.plain_thresholds(inner._threshold_value), inner._threshold_dim  # pylint: disable=protected-access
+    else:
+      inner_values, slot_dim = wrappers.plain_thresholds(inner._bin_values), inner._bin_dim  # pylint: disable=protected-access
+      if inner_values is not None and np.isnan(np.asarray(inner_values, np.float64)).any():
+        return None
+    if values is None or inner_values is None or event_dim == slot_dim or e in (event_dim, slot_dim):
+      return None
+    pairs = {}
+    for name in predictions.keys():
+      if name not in targets.keys():
+        continue
+      p, t = base._named(predictions[name], name), base._named(targets[name], name)  # pylint: disable=protected-access
+      if (e not in p.dims or e in t.dims or {event_dim, slot_dim} & (set(p.dims) | set(t.dims)) or not set(t.dims) <= set(p.dims)
+          or str(p.dtype) not in ('float32', 'float64') or str(t.dtype) not in ('float32', 'float64')
+          or not 1 <= p.sizes[e] <= _hip.EPC_MAX_MEMBERS):
+        return None
+      pairs[name] = (p, t)
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on (the host route says so where it needs one)
+      return None
+    if not engine.ens_prob_available(ctx):
+      return None
+    out = {}
+    inner_key = (type(inner).__name__, inner.unique_name_suffix)
+    for name, (p, t) in pairs.items():
+      try:
+        table = lazy.ens_prob_slot_table(mean, inner, p.sizes[e], e, slot_dim, like=p.data)
+      except (ValueError, KeyError, TypeError, AssertionError):  # (what the host route raises, it raises itself)
+        return None
+      if table is None:
+        return None
+      out[name] = lazy.ens_prob_contingency_statistic(_CELL_INDEX[type(self)], p, t, e, event_dim, values, slot_dim, table[1], table[0],
+                                                      (outer, mean, inner), inner_key=inner_key)
+    return out
+
 
 class TruePositives(_Indicator):
   """Predicted and observed (categorical.py:25-42)."""

@@ -82,6 +82,15 @@ class WrappedStatistic(base.Statistic):
       out = fused(self.transform, predictions, targets)
       if out is not None:
         return out
+    # ... or behind this wrapper and the two inside it, when this is the outermost of exactly three around it (categorical._Indicator
+    # behind ContinuousToBinary('both') -> EnsembleMean -> ContinuousToBinary / ContinuousToBins('predictions'))
+    mid = self.statistic
+    if type(mid) is WrappedStatistic and type(mid.statistic) is WrappedStatistic:  # pylint: disable=unidiomatic-typecheck
+      fused = getattr(mid.statistic.statistic, 'compute_with_chain', None)
+      if fused is not None:
+        out = fused((self.transform, mid.transform, mid.statistic.transform), predictions, targets)
+        if out is not None:
+          return out
     if self.transform.which in ('predictions', 'both'):
       predictions = xarray_tree.map_structure(self.transform.transform_fn, _as_tree(predictions))
     if self.transform.which in ('targets', 'both'):

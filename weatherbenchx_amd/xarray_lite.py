@@ -80,6 +80,8 @@ def _where(cond, a, b):
     if not _is_torch(a):
       a = t.as_tensor(a, device=dev, dtype=b.dtype if _is_torch(b) else None)
     if not _is_torch(b):
+      if isinstance(b, (float, np.floating)) and not a.is_floating_point():
+        a = a.to(t.float64)  # as np.where promotes: a NaN fill cannot live in a Boolean or integer tensor (it would turn into True / 0)
       b = t.as_tensor(b, device=dev, dtype=a.dtype)
     return t.where(cond.bool(), a, b)
   return np.where(cond, a, b)
