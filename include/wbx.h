@@ -583,6 +583,40 @@ int wbx_ens_prob_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int 
                                      const int32_t* slots /* DEVICE int32[2 * nslot]: lo, hi */, const void* p, const void* t,
                                      const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: SEEPS from a per-place score table (joined ABI 13) ----------------------------------------------------
+ * The stable equitable error in probability space (categorical.py:104-304) of a prediction p against a target t: both are put
+ * into a category against the dry threshold and the point's climatological wet threshold, and the pair of categories picks one of
+ * nine float64 scores of the PLACE out of a table the host has evaluated, instead of six float64 indicator fields, six products
+ * with broadcast coefficient fields, an aligned copy of the wet thresholds and a Boolean mask per chunk.
+ * `wet` is input 2 of the plan (key_off[2], depth_off[2], xstride[2], the gather tables; zero strides where it does not vary), in
+ * the input type.  `table` is DEVICE float64 and the kernel takes it as opaque numbers: cell (f, o) -- f the category of p, o the
+ * category of t -- of the point (key k, depth d, x) is
+ *     table[key_off[2][k] + depth_off[2][d] + x * xstride[2] + (3 * f + o) * cell_stride],
+ * input 2's address WITHOUT the gather term: the gather selects the time of year, which the table does not depend on.
+ * Category of a value v (p or t) against w = the point's `wet`, every comparison in the input type T, the dry threshold rounded
+ * to nearest into T first (for float32 inputs that is NOT the float64 comparison: float32(0.00025) > 0.00025, and the value
+ * float32(0.00025) is dry here):
+ *     0 (dry)    v <= (T)dry_threshold          (tested first)
+ *     1 (light)  v >  (T)dry_threshold && v < w
+ *     2 (heavy)  v >= w
+ *     none       otherwise -- a NaN w with a value that is not dry: the point takes cell (0, 0)
+ * so -0.0 and -inf are dry and +inf is heavy unless w is NaN.  PRECONDITION (the caller's, not checked): w > dry_threshold in T, or
+ * w is NaN, at every point; a value could otherwise be dry and heavy at once, which the table cannot express.
+ * Point value: NaN where p or t is NaN, by an explicit test; the table entry otherwise, handed on as it is (NaN, inf included).
+ * ONE value lane.  Count lanes, WBX_FLAG_MASKED, WBX_FLAG_SKIPNA and partial_out[nkey][nchunk][lanes_total][nj] are those of
+ * wbx_det_partial with one lane (wbx_s1_partial_len with lanes = 1; wbx_contract and wbx_contract_bits serve it unchanged): a
+ * masked-out point contributes exactly 0 whatever its table entry is, a NaN value poisons its partial without flags and under
+ * MASKED alone and is counted out under SKIPNA.  Sums are float64 in a fixed order, nothing is added atomically: the partial is a
+ * function of the inputs and the plan, bit for bit.
+ * Refused (WBX_ERR_INVALID, output untouched): an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, a
+ * NULL p, t, wet or table, plane_rows != 0 or x_weights.  vec = 4 is honoured for the p / t / wet loads where x is summed and ignored
+ * where x is kept.  nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_SEEPS_LANES 1
+#define WBX_SEEPS_CELLS 9 /* (category of p, category of t), cell 3 * f + o */
+int wbx_seeps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, double dry_threshold, const void* p,
+                      const void* t, const void* wet, const double* table /* DEVICE float64 */, int64_t cell_stride,
+                      const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -790,7 +824,7 @@ int wbx_det_spectrum_slabs(wbx_ctx* ctx, const wbx_s1_plan* plan, int func /* WB
  * a chunk is then a few microseconds whatever the number of metrics, variables and aggregators (a public-benchmark chunk is
  * ~0.35 ms of kernel against 0.3-0.45 ms of Python bookkeeping through the per-call path).
  *   calls[i]   = {fn, nargs, args[]}: entry point WBX_FN_* with its arguments in declaration order, each as the 64-bit pattern
- *                of the value (pointers as addresses, integers sign-extended);
+ *                of the value (pointers as addresses, integers sign-extended, a double as its IEEE bits);
  *   relocs[j]  = {call, arg, slot, offset}: before the calls run, calls[call].args[arg] = slots[slot] + offset -- the
  *                arguments that follow the chunk (input pointers, a plan variant);
  *   slots[]    = this chunk's values.
@@ -804,7 +838,7 @@ typedef enum wbx_fn {
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
-  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26
+  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -19,51 +19,6 @@
 
 namespace wbx {
 
-// 4-wide vector types that only promise element alignment: gfx950 global loads may be unaligned, so rows
-// that start at any element (e.g. 721-long latitude rows) still get one global_load_dwordx4 per lane.
-template <typename T>
-struct Vec4 {
-  typedef T type __attribute__((ext_vector_type(4), aligned(sizeof(T))));
-};
-
-template <typename T, int V>
-__device__ __forceinline__ void load_x(const void* base, int64_t off, int64_t x, int64_t xs, T (&v)[V]) {
-  const T* p = reinterpret_cast<const T*>(base) + off;
-  if constexpr (V == 4 && sizeof(T) == 1) {
-    // four mask bytes = one aligned dword (the planner only picks vec = 4 when every mask row starts 4-byte aligned)
-    if (xs == 1) {
-      const uint32_t q = *reinterpret_cast<const uint32_t*>(p + x);
-      v[0] = (T)(q & 0xffu);
-      v[1] = (T)((q >> 8) & 0xffu);
-      v[2] = (T)((q >> 16) & 0xffu);
-      v[3] = (T)(q >> 24);
-    } else {
-      T s = p[0];
-      v[0] = v[1] = v[2] = v[3] = s;
-    }
-  } else if constexpr (V == 4) {
-    if (xs == 1) {
-      using V4 = typename Vec4<T>::type;
-      const V4 q = __builtin_nontemporal_load(reinterpret_cast<const V4*>(p + x));  // see ld_stream (element-aligned type)
-      v[0] = q.x;
-      v[1] = q.y;
-      v[2] = q.z;
-      v[3] = q.w;
-    } else {  // xs == 0: broadcast along x
-      T s = p[0];
-      v[0] = v[1] = v[2] = v[3] = s;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if constexpr (sizeof(T) > 1)
-        v[k] = ld_stream(p + (x + k) * xs);
-      else
-        v[k] = p[(x + k) * xs];  // mask bytes are re-read by every depth row: keep them cached
-    }
-  }
-}
-
 // FUNC: 0 = DET3 (p,t), 1 = DET6 (p,t,c), 2 = PASS1 (p).
 // MM: 0 = no count lanes; 1 = mask only (ONE count lane shared by every value lane: validity does not depend on the
 // statistic); 2 = skipna without a mask, 3 = skipna with a mask (one count lane per value lane: a NaN may hit some

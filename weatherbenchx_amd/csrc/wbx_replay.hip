@@ -2,6 +2,7 @@
 // Host code only.  Every entry is dispatched through the entry point's OWN prototype: the parameter types are deduced from
 // the function, each 64-bit pattern is converted to the parameter it stands for, and a record whose argument count does not
 // match the prototype is refused.
+#include <cstring>
 #include <type_traits>
 #include <utility>
 
@@ -13,7 +14,12 @@ template <typename T>
 static inline T replay_arg(uint64_t v) {
   if constexpr (std::is_pointer_v<T>)
     return reinterpret_cast<T>(static_cast<uintptr_t>(v));
-  else
+  else if constexpr (std::is_floating_point_v<T>) {  // a double travels as its IEEE bits (wbx_seeps_partial's dry threshold)
+    static_assert(sizeof(T) == sizeof(uint64_t), "only double arguments are recorded");
+    T d;
+    memcpy(&d, &v, sizeof(d));
+    return d;
+  } else
     return static_cast<T>(static_cast<int64_t>(v));
 }
 
@@ -65,6 +71,7 @@ extern "C" int wbx_chunk_replay(wbx_call* calls, int32_t ncalls, const wbx_reloc
       WBX_REPLAY_CASE(WBX_FN_ENS_WASSERSTEIN_PARTIAL, wbx_ens_wasserstein_partial)
       WBX_REPLAY_CASE(WBX_FN_ENS_INTERVAL_PARTIAL, wbx_ens_interval_partial)
       WBX_REPLAY_CASE(WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL, wbx_ens_prob_contingency_partial)
+      WBX_REPLAY_CASE(WBX_FN_SEEPS_PARTIAL, wbx_seeps_partial)
       WBX_REPLAY_CASE(WBX_FN_CONTRACT, wbx_contract)
       WBX_REPLAY_CASE(WBX_FN_CONTRACT_BITS, wbx_contract_bits)
       WBX_REPLAY_CASE(WBX_FN_DET_BINNED, wbx_det_binned)

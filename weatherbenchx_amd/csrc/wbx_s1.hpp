@@ -41,6 +41,10 @@ struct S1Args {
   // map kernels (wbx_ens2_partial: the target ensemble size)
   int32_t lane;
   int64_t ngd_t;  // wbx_ens2_partial: element stride between target members
+  // wbx_seeps_partial: the score table, the element stride between its cells, the dry threshold
+  const double* table;
+  int64_t cell_stride;
+  double dry;
 };
 
 // Row base offsets (elements) of every input for (key, depth row).
@@ -50,12 +54,22 @@ __device__ __forceinline__ void key_bases(const S1Args& a, int64_t key, int64_t 
   for (int i = 0; i < WBX_MAX_INPUTS; ++i) kb[i] = (i < NIN || i == 3) && a.key_off[i] ? a.key_off[i][key] : 0;
 }
 
-template <int NIN>
+// An Op that addresses a second array by input 2's row WITHOUT the gather term (the score table of wbx_seeps.hip, which does not
+// depend on the time of year the gather selects) declares `static constexpr bool PLAIN_ROW2 = true`: its row offsets have one slot
+// more, ro[WBX_MAX_INPUTS], that holds it.
+template <class Op, class = void>
+struct op_ro_slots : std::integral_constant<int, WBX_MAX_INPUTS> {};
+template <class Op>
+struct op_ro_slots<Op, std::void_t<decltype(Op::PLAIN_ROW2)>> : std::integral_constant<int, WBX_MAX_INPUTS + (Op::PLAIN_ROW2 ? 1 : 0)> {};
+
+template <int NIN, int NRO>
 __device__ __forceinline__ void row_bases(const S1Args& a, const int64_t (&kb)[WBX_MAX_INPUTS], int64_t key,
-                                          int64_t d, int64_t (&ro)[WBX_MAX_INPUTS]) {
+                                          int64_t d, int64_t (&ro)[NRO]) {
+  static_assert(NRO == WBX_MAX_INPUTS || NRO == WBX_MAX_INPUTS + 1, "row offsets: the inputs, and input 2's ungathered row at most");
 #pragma unroll
   for (int i = 0; i < WBX_MAX_INPUTS; ++i)
     ro[i] = kb[i] + (((i < NIN || i == 3) && a.depth_off[i]) ? a.depth_off[i][d] : 0);
+  if constexpr (NRO > WBX_MAX_INPUTS) ro[WBX_MAX_INPUTS] = ro[2];
   if (NIN > 2 && a.gtab) ro[2] += a.gtab[(int64_t)(a.gk ? a.gk[key] : 0) * a.ngd + (a.gd ? a.gd[d] : 0)];
 }
 
@@ -83,6 +97,7 @@ struct op_has_mrow<Op, std::void_t<decltype(Op::MROW_OK)>> : std::integral_const
 template <class Op, int V, bool MROW = false>
 __global__ void __launch_bounds__(256, Op::MIN_WAVES) s1_xr_kernel(S1Args a) {
   constexpr int NA = Op::NACC;
+  constexpr int NRO = op_ro_slots<Op>::value;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int nwave = blockDim.x >> 6;
@@ -110,14 +125,14 @@ __global__ void __launch_bounds__(256, Op::MIN_WAVES) s1_xr_kernel(S1Args a) {
   // resolves the wave's l-th row up front and the sweep broadcasts the results (configs[1]: 4.05 -> 3.9 ms).
   for (int64_t dbatch = d0 + wave; dbatch < d1; dbatch += (int64_t)64 * nwave) {
     const int64_t dmine = dbatch + (int64_t)lane * nwave;
-    int64_t rov[WBX_MAX_INPUTS];
+    int64_t rov[NRO];
     row_bases<Op::NIN>(a, kb, key, dmine < d1 ? dmine : d1 - 1, rov);
     const int64_t left = (d1 - dbatch + nwave - 1) / nwave;
     const int nrow = (int)(left < 64 ? left : 64);
     for (int l = 0; l < nrow; ++l) {
-      int64_t ro[WBX_MAX_INPUTS];
+      int64_t ro[NRO];
 #pragma unroll
-      for (int i = 0; i < WBX_MAX_INPUTS; ++i) ro[i] = (i < Op::NIN || i == 3) ? readlane64(rov[i], l) : 0;
+      for (int i = 0; i < NRO; ++i) ro[i] = (i < Op::NIN || i >= 3) ? readlane64(rov[i], l) : 0;
 #pragma unroll Op::XR_UNROLL
       for (int64_t x = (int64_t)lane * V; x < a.nx; x += 64 * V) {
         if constexpr (MROW)
@@ -147,6 +162,7 @@ __global__ void __launch_bounds__(256, Op::MIN_WAVES) s1_xr_kernel(S1Args a) {
 template <class Op, int V>
 __global__ void __launch_bounds__(256, Op::MIN_WAVES) s1_xk_kernel(S1Args a) {
   constexpr int NA = Op::NACC;
+  constexpr int NRO = op_ro_slots<Op>::value;
   int64_t b = blockIdx.x;
   const int chunk = (int)(b % a.nchunk);
   b /= a.nchunk;
@@ -172,13 +188,13 @@ __global__ void __launch_bounds__(256, Op::MIN_WAVES) s1_xk_kernel(S1Args a) {
   if (V == 1 || nvalid == V) {
 #pragma unroll Op::XK_UNROLL
     for (int64_t d = d0; d < d1; ++d) {
-      int64_t ro[WBX_MAX_INPUTS];
+      int64_t ro[NRO];
       row_bases<Op::NIN>(a, kb, key, d, ro);
       Op::template accum<V, true>(a, ro, x, acc);
     }
   } else {
     for (int64_t d = d0; d < d1; ++d) {
-      int64_t ro[WBX_MAX_INPUTS];
+      int64_t ro[NRO];
       row_bases<Op::NIN>(a, kb, key, d, ro);
       for (int k = 0; k < nvalid; ++k)
         Op::template accum<1, true>(a, ro, x + k, reinterpret_cast<double(&)[1][NA]>(acc[k]));
@@ -339,6 +355,53 @@ __global__ void __launch_bounds__(1024, 6) s1_xp_kernel(S1Args a, int R) {  // <
     double* o = a.out + ((key * a.nchunk + chunk) * NA) * a.nx + tid;
 #pragma unroll
     for (int l = 0; l < NA; ++l) o[(int64_t)l * a.nx] = acc[l];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// V consecutive x of one row, for the Ops of wbx_det.hip and wbx_seeps.hip.
+// 4-wide vector types that only promise element alignment: gfx950 global loads may be unaligned, so rows
+// that start at any element (e.g. 721-long latitude rows) still get one global_load_dwordx4 per lane.
+template <typename T>
+struct Vec4 {
+  typedef T type __attribute__((ext_vector_type(4), aligned(sizeof(T))));
+};
+
+template <typename T, int V>
+__device__ __forceinline__ void load_x(const void* base, int64_t off, int64_t x, int64_t xs, T (&v)[V]) {
+  const T* p = reinterpret_cast<const T*>(base) + off;
+  if constexpr (V == 4 && sizeof(T) == 1) {
+    // four mask bytes = one aligned dword (the planner only picks vec = 4 when every mask row starts 4-byte aligned)
+    if (xs == 1) {
+      const uint32_t q = *reinterpret_cast<const uint32_t*>(p + x);
+      v[0] = (T)(q & 0xffu);
+      v[1] = (T)((q >> 8) & 0xffu);
+      v[2] = (T)((q >> 16) & 0xffu);
+      v[3] = (T)(q >> 24);
+    } else {
+      T s = p[0];
+      v[0] = v[1] = v[2] = v[3] = s;
+    }
+  } else if constexpr (V == 4) {
+    if (xs == 1) {
+      using V4 = typename Vec4<T>::type;
+      const V4 q = __builtin_nontemporal_load(reinterpret_cast<const V4*>(p + x));  // see ld_stream (element-aligned type)
+      v[0] = q.x;
+      v[1] = q.y;
+      v[2] = q.z;
+      v[3] = q.w;
+    } else {  // xs == 0: broadcast along x
+      T s = p[0];
+      v[0] = v[1] = v[2] = v[3] = s;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if constexpr (sizeof(T) > 1)
+        v[k] = ld_stream(p + (x + k) * xs);
+      else
+        v[k] = p[(x + k) * xs];  // mask bytes are re-read by every depth row: keep them cached
+    }
   }
 }
 
@@ -670,14 +733,18 @@ __global__ void __launch_bounds__(256) s1_map_kernel(S1Args a) {
 }
 
 // Launch helpers -----------------------------------------------------------------------------
-template <class Op, int V>
+// XK false: the caller never comes here with x kept, and no x-kept kernel is built for this (Op, V).
+template <class Op, int V, bool XK = true>
 int launch_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, S1Args& a, bool mask_row_in_lds = false) {
   bool done;
   if (int rc = s1_zero_if_empty(ctx, plan, Op::NACC, a.out, &done); rc || done) return rc;
   int64_t grid;
   if (int rc = s1_grid(plan, plan->x_kept ? (int64_t)plan->block_threads * V : 0, a, &grid)) return rc;
   if (plan->x_kept) {
-    hipLaunchKernelGGL((s1_xk_kernel<Op, V>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a);
+    if constexpr (XK)
+      hipLaunchKernelGGL((s1_xk_kernel<Op, V>), dim3((unsigned)grid), dim3(plan->block_threads), 0, ctx->stream, a);
+    else
+      return fail(WBX_ERR_INVALID, "internal: x kept on a launch path built without its kernel");
   } else {
     if constexpr (op_has_mrow<Op>::value) {
       if (mask_row_in_lds) {

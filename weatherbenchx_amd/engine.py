@@ -518,6 +518,16 @@ def ens_prob_available(ctx) -> bool:
     return False
 
 
+def seeps_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_seeps_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_seeps_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -800,6 +810,7 @@ EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_str
 VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
 IvlArgs = collections.namedtuple('IvlArgs', 'params')  # a HOST array of three _hip.IvlLaneStruct: no device buffer to keep
+SeepsArgs = collections.namedtuple('SeepsArgs', 'dry table cell_stride')
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -922,6 +933,41 @@ def _ivl_operands(ctx, devs, func, ens, cat, mdim):
   return bin(lanes).count('1'), IvlEnsArgs(m, devs[0].layout.stride(mdim), lanes), IvlArgs(params)
 
 
+def place_block(strides: dict, sizes: dict, place_dims):
+  """The dims `place_dims` of an array with these element strides as ONE dense block that starts at stride 1 -> (the dims from the
+  outermost to the innermost, the block's length), or None where they are not one (dims of size 1 do not matter)."""
+  live = sorted((d for d in place_dims if int(sizes[d]) != 1), key=lambda d: strides.get(d, 0))
+  run = 1
+  for d in live:
+    if strides.get(d, 0) != run:
+      return None
+    run *= int(sizes[d])
+  return tuple(d for d in place_dims if d not in live) + tuple(reversed(live)), run
+
+
+def _seeps_operands(ctx, devs, func, ens, cat, mdim):
+  """`cat` = {'dry_threshold', 'table' (float64 [3, 3, *place shape], categorical.seeps_score_table), 'place_dims', 'device_tables'
+  (a dict the caller keeps: one upload per device and layout)}.  The table goes up with the strides the wet thresholds' device
+  layout has along the place dims, cell by cell: the kernel reads cell c of a point at input 2's ungathered address + c * block."""
+  if devs[2] is None:
+    raise ValueError('SEEPS needs the wet thresholds (input 2)')
+  table = np.asarray(cat['table'], np.float64)
+  place_dims = tuple(cat['place_dims'])
+  sizes = dict(zip(place_dims, table.shape[2:]))
+  strides = {d: devs[2].layout.stride(d) for d in place_dims}
+  block = place_block(strides, sizes, place_dims)
+  if block is None or table.shape[:2] != (3, 3):
+    raise ValueError(f'the dims {place_dims} of the wet thresholds are not one dense block as they are stored (strides {strides})')
+  order, length = block
+  key = (ctx.device_id, order)
+  buf = cat['device_tables'].get(key)
+  if buf is None:
+    cells = table.reshape((_hip.SEEPS_CELLS,) + table.shape[2:])
+    cells = np.ascontiguousarray(np.transpose(cells, (0,) + tuple(1 + place_dims.index(d) for d in order)))
+    buf = cat['device_tables'][key] = ctx.upload(cells)
+  return _hip.SEEPS_LANES, None, SeepsArgs(float(cat['dry_threshold']), buf, int(length))
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -962,6 +1008,10 @@ _KINDS = {
     'ivl': _Kind(_ivl_operands, (),  # (the lane parameters are host values: a recorded chunk keeps the array itself)
                  lambda d, out, dt, func, ens, cat:
                  ('wbx_ens_interval_partial', (dt, *map(int, ens), cat.params, d[0], d[1], d[2], d[3], out))),
+    'seeps': _Kind(_seeps_operands, ('table',),
+                   lambda d, out, dt, func, ens, cat:
+                   ('wbx_seeps_partial', (dt, C.c_double(cat.dry), d[0], d[1], d[2], _table_ptr(cat.table), int(cat.cell_stride), d[3],
+                                          out))),
 }
 
 
@@ -1682,7 +1732,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   stage 2) / 'epc' (contingency tables of ensemble event probabilities, wbx_ens_prob_contingency_partial: the operands of 'erps' --
   `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag)} --, `cat` = {'thresholds': float64 ndarray of K event
   thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts}, K * J <= _hip.EPC_MAX_PAIRS; value lane
-  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2).
+  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2) / 'seeps' (SEEPS from a per-place score table,
+  wbx_seeps_partial: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table' (float64
+  [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1756,7 +1808,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
   replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in _KINDS[kind].keep),
-              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None)
+              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None,
+              # (a mask that outlives the chunk: the places whose dry fraction is in range, kind 'seeps')
+              devs[3] if (mask is not None and cat and cat.get('mask_da') is mask) else None)
   bin_shape = w_buf.bin_shape
   s2 = planner.build_s2_plan(plan, nl_total, w_buf.shape[-1])
   # Under skipna a twin launch does not form the masked spread / variance (wbx.h): fine while those are statistics of a

@@ -64,6 +64,10 @@ FUSED_INTERVALS = os.environ.get('WBX_FUSED_INTERVALS', '1') != '0'
 # the [K, M, frame] and [K, J, frame] indicator arrays on the host and reduce them as before wbx_ens_prob_contingency_partial existed
 # (A/B timing, tests).
 FUSED_ENS_PROB = os.environ.get('WBX_FUSED_ENS_PROB', '1') != '0'
+# False (WBX_FUSED_SEEPS=0): SEEPS builds an aligned copy of the wet thresholds, six float64 indicator arrays, their six products with
+# broadcast coefficient fields and a Boolean mask per chunk and variable, reduced as before wbx_seeps_partial existed (A/B timing,
+# tests).
+FUSED_SEEPS = os.environ.get('WBX_FUSED_SEEPS', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -216,7 +220,8 @@ class FusedGroup:
     self.ens = ens  # {'member_dim', 'M'}; kind 'enrg': + {'fair' (None: no spread statistic has said yet), 'norm_dims', 'norm_sizes'};
     # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}; kinds 'ens2', 'wass': + {'N'}
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
-    # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join
+    # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
+    # 'device_tables', 'host', 'mask_da'} (seeps_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -242,6 +247,8 @@ class FusedGroup:
 
   @property
   def mask(self) -> xr.DataArray | None:
+    if self.kind == 'seeps' and self.cat.get('mask_da') is not None:
+      return self.cat['mask_da']
     if 'mask' in self.coords:
       cd, cv = self.coords['mask']
       # a mask that was built in HBM (data.add_nan_mask_to_data on device payloads) is consumed there
@@ -254,6 +261,8 @@ class FusedGroup:
       return [self.p, self.t], 0
     if self.kind == 'ivl':
       return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
+    if self.kind == 'seeps':
+      return [self.p, self.t, self.clim.source], 0
     if self.clim is not None:
       return [self.p, self.t, self.clim.source], _hip.DET6
     return [self.p, self.t], _hip.DET3
@@ -269,6 +278,9 @@ class FusedGroup:
     if self.kind == 'ivl':  # one launch for every lane asked for so far, the climatology gathered in place like ACC's
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                  skipna=skipna, clim=self.clim, ens=self.ens, cat=self.cat)
+    if self.kind == 'seeps':  # the wet thresholds gathered in place like ACC's climatology; the score table addresses their places
+      return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
+                                 skipna=skipna, clim=self.clim, ens=None, cat=self.cat, may_align=False)
     # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
     # group are its own); 'cat', 'cont', 'epc': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
@@ -371,6 +383,9 @@ class FusedGroup:
         stat = multivariate.EnergyScoreSpread(dim=list(ens['norm_dims']), ensemble_dim=ens['member_dim'], fair=ens['fair'] is not False)
       out = stat.host_per_variable(self.p, self.t)
       return out.transpose(*self.dims).data
+    if self.kind == 'seeps':  # the host route's per-point values (categorical.SEEPS._one), in whatever array type it gives
+      out = self.cat['host'](self.p, self.t)
+      return out.transpose(*self.dims).data
     if self.kind == 'vgrm':  # the host route's per-point values, as for 'enrg'
       from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
       ens = self.ens
@@ -442,7 +457,10 @@ def _regather(p_new, g):
     return None
 
 
-def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, *, func, mask, skipna, clim, ens, cat=None):
+def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, *, func, mask, skipna, clim, ens, cat=None,
+                        may_align=True):
+  """`may_align` False: a gather along the innermost dim is the caller's error (kind 'seeps': its score table is addressed by the
+  climatology's own places, which an aligned copy does not have)."""
   gather, inputs = _gather_spec(clim, inputs, dims)
   rec = replay.active() if clim is not None else None
   if rec is not None:  # a chunk that is being recorded: what its gather plans have to be rebuilt from for the next chunk
@@ -452,7 +470,7 @@ def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, 
     return engine.reduce_statistics(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                     skipna=skipna, gather=gather, ens=ens, cat=cat)
   except ValueError as e:
-    if clim is None or 'innermost' not in str(e):
+    if clim is None or 'innermost' not in str(e) or not may_align:
       raise
     # the selection runs along the contiguous dim: align the climatology first, then fuse as usual
     aligned = clim.aligned_view()
@@ -1095,6 +1113,27 @@ def interval_statistic(p, t, clim_ref: ClimatologyRef | None, ensemble_dim: str,
     names = None if bit == _hip.IVL_COVERED else frozenset(p._coords) | frozenset(clim_ref._coords)  # pylint: disable=protected-access
     return LazyInterval(grp, bit, name=p.name, coord_names=names)
   raise ValueError(f'more than {IVL_MAX_GROUPS} interval groups of one (predictions, targets) pair')
+
+
+def seeps_statistic(p, t, clim_ref: ClimatologyRef, *, table, place_dims, dry_threshold: float, device_tables: dict, mask, extra_coords,
+                    host, clim_key=None, name=None, mask_da=None) -> xr.DataArray:
+  """SEEPS of (p, t) as a LazyStatistic on a FusedGroup of kind 'seeps' (wbx_seeps_partial).  `clim_ref`: the wet thresholds aligned
+  with p's valid times (gathered in place); `table`: categorical.seeps_score_table of the places' dry fractions over `place_dims`;
+  `device_tables`: the dict its device copies are kept in (the statistic's, one upload per variable, device and layout); `mask`:
+  (dims, Boolean values), the host route's `mask` coordinate -- the group reduces under it (`mask_da`: the same as a DataArray that
+  outlives the chunk and carries its device copy); `extra_coords`: the coordinates the host
+  route's selection of the wet thresholds adds; `host(p, t)`: the host route, which whoever reads the per-point values gets.  One
+  group per (p, t, `clim_key`).  Raises ValueError where the wet thresholds do not broadcast against the frame of (p, t)."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  cat = {'dry_threshold': float(dry_threshold), 'table': table, 'place_dims': tuple(place_dims), 'device_tables': device_tables,
+         'host': host, 'mask_da': mask_da}
+  grp = _group_for('seeps', p, t, clim_key=('seeps', clim_key), cat=cat)
+  if not grp.attach_climatology(clim_ref, clim_key):
+    raise ValueError(f'wet-threshold dims {clim_ref.aligned_dims()} do not broadcast against the statistic dims {grp.dims}')
+  for k, v in extra_coords.items():
+    grp.coords.setdefault(k, v)
+  grp.coords['mask'] = (tuple(mask[0]), mask[1])
+  return LazyStatistic(grp, 0, name=p.name if name is None else name)
 
 
 ENS2_LANE = {'CRPSSkill': 0, 'UnbiasedEnsembleMeanSquaredError': 1}

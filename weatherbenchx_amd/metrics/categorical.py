@@ -8,7 +8,8 @@ statistic), and every score below is a formula on those four means.  Inputs come
 SEEPS and the interval statistics (Confident / Covered / JaccardDistant -> Opportunism) follow the same pattern with a
 climatology beside the chunk.  The Aggregator gets the sums of the three interval statistics of one (predictions, targets,
 climatology) from one launch of wbx_ens_interval_partial (lazy.interval_statistic), which sorts a point's members once; the per-point
-values anybody reads are Boolean as before.
+values anybody reads are Boolean as before.  The sums of SEEPS come from wbx_seeps_partial (lazy.seeps_statistic), which looks the score
+of a point up in a table of the nine scores of its place (seeps_score_table); the per-point values are the host route's as before.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ import numpy as np
 from weatherbenchx_amd import _hip
 from weatherbenchx_amd import engine
 from weatherbenchx_amd import lazy
+from weatherbenchx_amd import planner
 from weatherbenchx_amd import xarray_lite as xr
 from weatherbenchx_amd.metrics import base
 from weatherbenchx_amd.metrics import wrappers
@@ -481,6 +483,31 @@ class Opportunism(base.PerVariableMetric):
     return out
 
 
+def seeps_score_table(p1, min_p1: float, max_p1: float) -> np.ndarray:
+  """float64 [3, 3, *p1.shape]: what `SEEPS._one` gives a point of the place with dry fraction `p1` whose forecast is in category f and
+  whose observation is in category o (0 dry, 1 light, 2 heavy), as T[f, o].  It is `_one`'s own expression, evaluated once per
+  category pair on whatever holds `p1` (a NumPy array or a tensor, in the type it has there: the two libraries do not round
+  `3 / (1 - p1)` alike) with the six indicators as float64 fields of zeros and ones, so everything that expression does comes along
+  bit for bit: the sum of six `0 * coefficient` terms on the diagonal, `0 * inf` for a p1 of 0 or 1, a NaN p1, NaN outside
+  [min_p1, max_p1].  wbx_seeps_partial looks the score of a point up in it (include/wbx.h)."""
+  if not isinstance(p1, xr.DataArray):
+    p1 = xr.DataArray(p1, dims=tuple(f'place_{i}' for i in range(len(xr._shape(p1)))))  # pylint: disable=protected-access
+  everywhere = p1.isnull() | ~p1.isnull()
+  indicator = lambda yes: (everywhere if yes else ~everywhere).astype(np.float64)
+  out = np.empty((3, 3) + tuple(p1.shape), np.float64)
+  with np.errstate(all='ignore'):
+    mask = (p1 >= min_p1) & (p1 <= max_p1)
+    for f in range(3):
+      f_dry, f_light, f_heavy = (indicator(f == c) for c in range(3))
+      for o in range(3):
+        o_dry, o_light, o_heavy = (indicator(o == c) for c in range(3))
+        result = 0.5 * (f_dry * o_light * (1 / (1 - p1)) + f_dry * o_heavy * (4 / (1 - p1))
+                        + f_light * o_dry * (1 / p1) + f_light * o_heavy * (3 / (1 - p1))
+                        + f_heavy * o_dry * (1 / p1 + 3 / (2 + p1)) + f_heavy * o_light * (3 / (2 + p1)))
+        out[f, o] = xr._to_numpy(result.where(mask, np.nan).transpose(*p1.dims).data)  # pylint: disable=protected-access
+  return out
+
+
 class SEEPS(base.Statistic):
   """Stable equitable error in probability space (Rodwell et al. 2010) of precipitation: forecast and observation are each put
   into dry (<= dry_threshold_mm, in metres here) / light / heavy (>= the climatological wet threshold at the valid time), and the
@@ -493,7 +520,10 @@ class SEEPS(base.Statistic):
 
   `climatology` holds `<variable>_seeps_dry_fraction` and `<variable>_seeps_threshold` over (dayofyear, hour, latitude,
   longitude).  Places with p1 outside [min_p1, max_p1] are NaN, and the result carries that as a `mask` coordinate (combined with a
-  mask the predictions OR the targets already have) for `Aggregator(masked=True)`.  categorical.py:104-304."""
+  mask the predictions OR the targets already have) for `Aggregator(masked=True)`.  categorical.py:104-304.
+
+  Under the Aggregator the sums come from wbx_seeps_partial (`_fused`); `_one` is the host route, which everything the gate declines
+  takes and which whoever reads `.values` of the lazy result gets."""
 
   def __init__(self, variables: Sequence[str], climatology, dry_threshold_mm: Union[float, Sequence[float]] = 0.25,
                min_p1: Union[float, Sequence[float]] = 0.1, max_p1: Union[float, Sequence[float]] = 0.85):
@@ -511,8 +541,140 @@ class SEEPS(base.Statistic):
             f'_max_p1_{join(self._max_p1)}')
 
   def compute(self, predictions: Mapping[Hashable, xr.DataArray], targets: Mapping[Hashable, xr.DataArray]):
-    return {v: self._one(xr.as_dataarray(predictions[v]), xr.as_dataarray(targets[v]), v, dry, lo, hi)
-            for v, dry, lo, hi in zip(self._variables, self._dry_threshold_mm, self._min_p1, self._max_p1)}
+    out = {}
+    for v, dry, lo, hi in zip(self._variables, self._dry_threshold_mm, self._min_p1, self._max_p1):
+      p, t = xr.as_dataarray(predictions[v]), xr.as_dataarray(targets[v])
+      fused = self._fused(p, t, v, dry, lo, hi)
+      out[v] = fused if fused is not None else self._one(p, t, v, dry, lo, hi)
+    return out
+
+  def _fused(self, predictions, targets, variable, dry_threshold_mm, min_p1, max_p1):
+    """SEEPS of one variable as a lazy statistic that the Aggregator reduces with wbx_seeps_partial (lazy.seeps_statistic), or None
+    where the host route (`_one`) has to do it: the switch is off (WBX_FUSED_SEEPS=0); no device or library, or no such symbol in it;
+    predictions and targets that are not both float32 or both float64 over one frame (equal dims, sizes and labels); wet thresholds
+    that are neither float32 nor of that type (an upload must not round a threshold); a wet-threshold climatology whose dims are not
+    `dayofyear`, `hour` and dims of the statistic with equal labels; a dry fraction whose dims after the mean are not those place
+    dims; place dims that are not one dense block of the climatology as the device holds it; a climatology behind a slab pool; valid
+    times that vary along the innermost dim of the predictions; wet thresholds of which one that is not NaN is <= the dry threshold in
+    the type they are compared in (a value could be dry and heavy at once, which the score table cannot say); masks on both sides
+    (the host route raises).  What depends on the climatology alone -- the score table, that threshold check -- is kept per variable
+    and climatology OBJECT (its id and `_mutations`, as the device copies in `_wbx_dev` are): a payload changed in place behind the
+    object's back is not noticed.  The result has the host route's dims, name and coordinates, its `mask` coordinate among them, and its
+    `.values` are the host route's."""
+    if not lazy.FUSED_SEEPS:
+      return None
+    p, t = predictions, targets
+    dtype = str(p.dtype)
+    if dtype not in ('float32', 'float64') or str(t.dtype) != dtype or set(p.dims) != set(t.dims) or not p.dims:
+      return None
+    if 'mask' in p.coords and 'mask' in t.coords:
+      return None
+    try:
+      wet_da = xr.as_dataarray(self._climatology[f'{variable}_seeps_threshold'])
+      dry_da = xr.as_dataarray(self._climatology[f'{variable}_seeps_dry_fraction'])
+    except KeyError:
+      return None
+    if str(wet_da.dtype) not in ('float32', dtype) or isinstance(wet_da, lazy.ClimatologyRef):
+      return None
+    if not {'dayofyear', 'hour'} <= set(wet_da.dims) or not {'dayofyear', 'hour'} <= set(dry_da.dims):
+      return None
+    if not ('init_time' in p.coords and 'lead_time' in p.coords):
+      return None
+    place_dims = tuple(d for d in wet_da.dims if d not in ('dayofyear', 'hour'))
+    if not set(place_dims) <= set(p.dims):
+      return None
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+      return None
+    if not engine.seeps_available(ctx):
+      return None
+    memo = self.__dict__.setdefault('_fused_memo', {})  # per variable: what depends on the climatology alone
+    key = (variable, id(wet_da), wet_da.__dict__.get('_mutations', 0), id(dry_da), dry_da.__dict__.get('_mutations', 0), dtype,
+           dry_threshold_mm, min_p1, max_p1)
+    hit = memo.get(variable)
+    if hit is None or hit['key'] != key or hit['wet'] is not wet_da or hit['dry'] is not dry_da:
+      hit = memo[variable] = {'key': key, 'wet': wet_da, 'dry': dry_da, 'device_tables': {},
+                              'places': self._fused_places(wet_da, dry_da, place_dims, dtype, dry_threshold_mm, min_p1, max_p1)}
+    places = hit['places']  # {'table', 'in_range', 'p1_dims', 'masks'}
+    if places is None:
+      return None
+    # the places as the device will hold them: a host payload is uploaded in C order, a tensor in HBM is read where it lies
+    data = wet_da.data
+    if xr._is_torch(data) and data.is_cuda:  # pylint: disable=protected-access
+      strides = dict(zip(wet_da.dims, data.stride()))
+    else:
+      strides, run = {}, 1
+      for d in reversed(wet_da.dims):
+        strides[d], run = run, run * wet_da.sizes[d]
+    if engine.place_block(strides, wet_da.sizes, place_dims) is None:
+      return None
+    from weatherbenchx_amd import climatology_cache  # pylint: disable=g-import-not-at-top
+    try:
+      if climatology_cache.cache_for(wet_da) is not None:  # a slab pool stands in for the climatology: its places are the pool's
+        return None
+      ref = base.PerVariableStatisticWithClimatology.resolve_climatology(p, wet_da)
+      if ref.origin is not None or ref.source is not wet_da:
+        return None
+      frame_dims, frame_sizes, _ = lazy._stat_frame_walk([p, t])  # pylint: disable=protected-access
+      if frame_dims != p.dims:
+        return None
+      in_hbm = xr._is_torch(p.data) and p.data.is_cuda  # pylint: disable=protected-access
+      x_dim = planner.choose_x_dim(p.dims, frame_sizes, planner.layout_of(p.data, p.dims)) if in_hbm else p.dims[-1]
+      if x_dim in ref.over_dims:
+        return None
+      # the host route's mask and the coordinates its selection of the wet thresholds adds, from the labels alone
+      mask = xr.DataArray(places['in_range'], dims=places['p1_dims'])
+      for side in (p, t):
+        if 'mask' in side.coords:
+          mask = mask & side.coords['mask']
+      mask = mask.transpose(*[d for d in p.dims if d in mask.dims])
+      mask = (tuple(mask.dims), np.asarray(mask.values, dtype=bool))
+      mask_da = None
+      if 'mask' not in p.coords and 'mask' not in t.coords:
+        # the places in range and nothing else: ONE object per variable and dim order, so that its device copy is made once and
+        # a recorded chunk loop meets no upload
+        mask_da = places['masks'].setdefault(mask[0], xr.DataArray(mask[1], dims=mask[0]))
+        mask = (mask[0], mask_da.data)
+      valid_time = p['init_time'] + p['lead_time']
+      extra = {}
+      for name, labels in (('dayofyear', valid_time.dt.dayofyear), ('hour', valid_time.dt.hour)):
+        if name not in p.coords and name not in t.coords:
+          extra[name] = (tuple(labels.dims), np.asarray(labels.values))
+      host = lambda pp, tt: self._one(pp, tt, variable, dry_threshold_mm, min_p1, max_p1)
+      return lazy.seeps_statistic(p, t, ref, table=places['table'], place_dims=places['p1_dims'], dry_threshold=dry_threshold_mm / 1000.0,
+                                  device_tables=hit['device_tables'], mask=mask, mask_da=mask_da,
+                                  extra_coords=extra, host=host, clim_key=key, name=variable)
+    except (lazy._NeedsAlignment, ValueError, KeyError, _hip.WbxError):  # pylint: disable=protected-access  (the host route broadcasts, or says what is wrong)
+      return None
+
+  @staticmethod
+  def _fused_places(wet_da, dry_da, place_dims, dtype, dry_threshold_mm, min_p1, max_p1):
+    """What `_fused` needs of the climatology alone, once per variable: {'table': the score table of the places, 'in_range': the
+    places `_one` does not blank, 'p1_dims'}, or None where the fused route does not apply."""
+    p1 = dry_da.mean(('hour', 'dayofyear'))  # as `_one` forms it
+    if set(p1.dims) != set(place_dims):
+      return None
+    for d in place_dims:  # the dry fraction lies on the places of the wet thresholds
+      if (d in wet_da.coords) != (d in p1.coords) or (d in wet_da.coords and not xr._values_equal(wet_da.coords[d].values, p1.coords[d].values)):  # pylint: disable=protected-access
+        return None
+    # a value must never be dry and heavy at once: every wet threshold that is not NaN lies above the dry threshold, in the type
+    # the host route compares them in (a float32 field against float32 wet thresholds: float32; otherwise float64).  Decided where
+    # the thresholds lie and in their own type, without a copy: `limit` is the largest number of that type that is not above the dry
+    # threshold of the comparison type, so `wet <= limit` there is `wet <= dry` here.
+    wet = wet_da.data
+    wet_type = np.float32 if str(wet_da.dtype) == 'float32' else np.float64
+    dry = float(np.float32(dry_threshold_mm / 1000.0)) if (dtype == 'float32' and wet_type is np.float32) else dry_threshold_mm / 1000.0
+    limit = wet_type(dry)
+    if float(limit) > dry:
+      limit = np.nextafter(limit, wet_type(-np.inf))
+    with np.errstate(invalid='ignore'):
+      if bool((wet <= float(limit)).any()):  # (a NaN threshold compares false)
+        return None
+    p1 = p1.transpose(*place_dims)
+    with np.errstate(all='ignore'):
+      in_range = np.asarray(((p1 >= min_p1) & (p1 <= max_p1)).values, dtype=bool)
+    return {'table': seeps_score_table(p1, min_p1, max_p1), 'in_range': in_range, 'p1_dims': tuple(place_dims), 'masks': {}}
 
   @staticmethod
   def _categories(da: xr.DataArray, wet: xr.DataArray, dry_threshold_mm: float):

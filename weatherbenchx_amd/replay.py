@@ -59,6 +59,8 @@ def _arg64(arg, keepalive):
     return int(arg) & _MASK64
   if isinstance(arg, C.c_void_p):
     return int(arg.value or 0)
+  if isinstance(arg, (float, np.floating, C.c_double)):  # a double travels as its IEEE bits (include/wbx.h: wbx_call)
+    return int(np.float64(getattr(arg, 'value', arg)).view(np.uint64))
   obj = getattr(arg, '_obj', None)  # C.byref(struct)
   if obj is not None:
     keepalive.append(obj)
