@@ -617,6 +617,76 @@ int wbx_seeps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F3
                       const void* t, const void* wet, const double* table /* DEVICE float64 */, int64_t cell_stride,
                       const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: the three terms of the fractions skill score (joined ABI 13) -------------------------------------------
+ * SquaredFractionsError, SquaredPredictionFraction and SquaredTargetFraction (spatial.py:24-277) of a prediction p against a target
+ * t at ONE neighbourhood size n, in one sweep over p and t: the n x n neighbourhood means Pf, Tf of both fields are formed from
+ * sliding float64 window sums (cost per point independent of n) instead of four whole-array convolutions per size, and the three
+ * squares are summed like any other stage-1 statistic.
+ * The stencil runs along latitude and longitude, which the stage-1 plan cannot express (latitude is neither key, depth nor x there),
+ * so the entry has a plan of its own:
+ *   key    k in [0, nkey)     fields that get their own partials
+ *   depth  d in [0, ndepth)   fields summed inside the launch, in nchunk chunks of depth_chunk
+ *   (y, x) in [0, nlat) x [0, nlon)
+ * element address of input i (0 = p, 1 = t, 2 = mask) at (k, d, y, x):
+ *     in[i] + key_off[i][k] + depth_off[i][d] + y * lat_stride[i] + x * lon_stride[i]
+ * All tables are DEVICE pointers; a NULL table means zeros (a (latitude, longitude)-only mask is two strides and no tables).  Any
+ * strides are consumed in place.
+ * Per point (y, x), n odd and greater than 1, h = (n - 1) / 2, everything in float64:
+ *     S_p = sum of (double)p over the n x n window, NaN members taken as 0;   H_p = the number of NaN members in the window
+ *     longitude is cyclic in the window; latitude never has to wrap (every row whose window would is a border row)
+ *     Pf = (float)(S_p / (double)(n * n)), or NaN where H_p > 0;   Tf the same from t
+ *     border points -- y < h, y >= nlat - h, and x < h or x >= nlon - h unless wrap_longitude -- have Pf = Tf = 0 whatever the
+ *     window holds (a NaN included)
+ *     value lanes, in float32 arithmetic, then widened:  0 (Pf - Tf)^2,  1 Pf^2,  2 Tf^2          (WBX_FSS_LANES, part of the ABI)
+ * n == 1: Pf = p and Tf = t in the INPUT type (float64 stays float64: no float32 rounding), no border; the squares in that type.
+ * Count lanes follow the library's convention (none / one shared / one per value lane), exactly as wbx_contingency_partial words it:
+ * a NaN lane of a point poisons that lane of its partial without flags; under WBX_FLAG_MASKED alone a point contributes exactly 0
+ * where the mask is 0 and poisons where it is not; under WBX_FLAG_SKIPNA a NaN lane of a point is counted out of that lane.  Lane 1
+ * does not depend on t's NaNs, nor lane 2 on p's.  The mask is the mask OF THE STATISTIC (what spatial.get_fss_mask returns for this
+ * size): the kernel does not erode masks.
+ * partial_out[nkey][nlat][nchunk][lanes_total][nj], nj = nlon where x_kept, else 1: the stage-1 partial of a plan with nkey * nlat
+ * keys, latitude the fastest key index; wbx_s1_partial_len (with such a plan), wbx_contract and wbx_contract_bits serve it unchanged.
+ * Sums: a block of 256 threads owns a (key, chunk, band of B latitudes) and whole circles; a thread owns the columns l + 256 c.  The
+ * vertical window sums slide down the band (row y + h enters, row y - h leaves), the horizontal window is a difference of two values
+ * of an inclusive prefix over the circle.  The lanes of a row are summed over x as thread -> wave -> the four waves, the fields of a
+ * chunk in field order; that order does not depend on B.  No atomics: the result is a function of the inputs, the plan and n, bit for bit.
+ * B = WBX_FSS_MAX_BAND_ROWS, halved while B > WBX_FSS_MIN_BAND_ROWS, nkey * nchunk * ceil(nlat / B) < WBX_FSS_TARGET_BLOCKS and
+ * B / 2 >= 2 (n - 1) (the halo of n - 1 rows stays at most half a band).
+ * Accuracy.  Inputs whose window sums are exact in float64 (0 / 1 indicator fields -- what FSS gets -- and small integers): S is exact
+ * in any order, and the fraction is the float32 rounding of the correctly rounded float64 quotient of two integers.  Other inputs,
+ * u = 2^-53, M = max |x| over the field: a column sum has seen at most n + 2 B additions of partial sums below n M, a prefix value at
+ * most 7 + 6 + 4 + 1 additions of partial sums below nlon n M (its run, the wave scan, the waves in front, the offset; the bound allows
+ * 42), and the window is two prefix values, at most two totals and n columns:
+ *     |dS| <= u n M (n (n + 2 B) + 84 nlon + 8),     |d(S / n^2)| <= |dS| / n^2 + u |S| / n^2
+ * after which the float32 rounding of the fraction (half an ulp of float32; one ulp where dS moves the quotient across a tie)
+ * dominates.  +-inf inputs are outside the contract (the host route's running sums turn every later window of such a row into NaN;
+ * here inf - inf appears when the value leaves the window).
+ * Refused (WBX_ERR_INVALID, output untouched): an even n, n < 1, n > min(nlat, nlon) for n > 1, nlon > WBX_FSS_MAX_NLON (the circle's
+ * prefix lives in LDS), an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask.  nkey == 0 touches nothing;
+ * ndepth == 0, nlat == 0 or nlon == 0 zero the partial. */
+#define WBX_FSS_LANES 3
+#define WBX_FSS_MAX_NLON 2048
+#define WBX_FSS_MAX_BAND_ROWS 64
+#define WBX_FSS_MIN_BAND_ROWS 8
+#define WBX_FSS_TARGET_BLOCKS 1024
+typedef struct wbx_fss_plan {
+  int64_t nkey;
+  int64_t ndepth;
+  int64_t nlat;
+  int64_t nlon;
+  int32_t x_kept;         /* 1: keep one partial per longitude (nj = nlon); 0: sum longitude away (nj = 1) */
+  int32_t nchunk;         /* depth is cut into nchunk pieces of depth_chunk fields */
+  int64_t depth_chunk;
+  int64_t lat_stride[3];  /* 0 = p, 1 = t, 2 = mask (uint8) */
+  int64_t lon_stride[3];
+  const int64_t* key_off[3];   /* [nkey]   or NULL */
+  const int64_t* depth_off[3]; /* [ndepth] or NULL */
+  uint32_t flags;         /* WBX_FLAG_MASKED | WBX_FLAG_SKIPNA */
+  int32_t wrap_longitude; /* 0: the h outermost columns are border points too */
+} wbx_fss_plan;
+int wbx_fss_partial(wbx_ctx* ctx, const wbx_fss_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int n, const void* p, const void* t,
+                    const uint8_t* mask, double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -838,7 +908,7 @@ typedef enum wbx_fn {
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
-  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27
+  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

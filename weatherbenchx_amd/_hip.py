@@ -41,6 +41,9 @@ EPC_MAX_PAIRS = 16  # (event threshold, probability slot) pairs per launch (WBX_
 EPC_MAX_MEMBERS = 256  # (WBX_EPC_MAX_MEMBERS)
 SEEPS_LANES = 1  # wbx_seeps_partial (WBX_SEEPS_LANES)
 SEEPS_CELLS = 9  # cells of its score table: 3 * (category of p) + (category of t) (WBX_SEEPS_CELLS)
+FSS_LANES = 3  # wbx_fss_partial: (Pf - Tf)^2, Pf^2, Tf^2 (WBX_FSS_LANES)
+FSS_MAX_NLON = 2048  # the longitude circle's prefix lives in LDS (WBX_FSS_MAX_NLON)
+FSS_MAX_BAND_ROWS, FSS_MIN_BAND_ROWS, FSS_TARGET_BLOCKS = 64, 8, 1024  # (WBX_FSS_MAX_BAND_ROWS, ..._MIN_BAND_ROWS, ..._TARGET_BLOCKS)
 ENS_LANES = 5
 ENS2_LANES = 2  # wbx_ens2_partial: skill over (prediction, target) member pairs, unbiased MSE with both ensembles' counts
 ENS_SORT, ENS_PAIRWISE = 0, 1
@@ -63,7 +66,7 @@ EXPORTED_SYMBOLS = (
     'wbx_ens2_partial', 'wbx_cat_exceed_field', 'wbx_chunk_replay', 'wbx_host_transpose', 'wbx_clock_probe', 'wbx_det_spectrum_folded',
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
-    'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial',
+    'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -73,7 +76,7 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_memset': 15, 'wbx_memcpy_d2d': 16, 'wbx_ctx_wait_fence': 17, 'wbx_fence_record': 18, 'wbx_det_spectrum_folded': 19,
           'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
           'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25,
-          'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27}
+          'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -167,6 +170,24 @@ class S1PlanStruct(C.Structure):
   ]
 
 
+class FssPlanStruct(C.Structure):  # wbx_fss_plan
+  _fields_ = [
+      ('nkey', C.c_int64), ('ndepth', C.c_int64), ('nlat', C.c_int64), ('nlon', C.c_int64),
+      ('x_kept', C.c_int32), ('nchunk', C.c_int32), ('depth_chunk', C.c_int64),
+      ('lat_stride', C.c_int64 * 3), ('lon_stride', C.c_int64 * 3),
+      ('key_off', C.c_void_p * 3), ('depth_off', C.c_void_p * 3),
+      ('flags', C.c_uint32), ('wrap_longitude', C.c_int32),
+  ]
+
+
+def fss_band_rows(nkey: int, nchunk: int, nlat: int, n: int) -> int:
+  """Rows of a band of wbx_fss_partial (include/wbx.h says how the library picks them)."""
+  b = FSS_MAX_BAND_ROWS
+  while b > FSS_MIN_BAND_ROWS and nkey * nchunk * (-(-nlat // b)) < FSS_TARGET_BLOCKS and b // 2 >= 2 * (n - 1):
+    b //= 2
+  return b
+
+
 class S2PlanStruct(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('nA', 'nBk', 'nBr', 'nchunk', 'nlane', 'nj', 'nbin')] + [('sum_j', C.c_int32)]
 
@@ -253,6 +274,7 @@ def load_library():
         'wbx_ens_prob_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, i32, vp, vp, vp, vp, vp],
         'wbx_ens_interval_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlLaneStruct), vp, vp, vp, vp, vp],
         'wbx_seeps_partial': [vp, C.POINTER(S1PlanStruct), i32, C.c_double, vp, vp, vp, vp, i64, vp, vp],
+        'wbx_fss_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, vp, vp, vp, vp],
         'wbx_det_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, vp, vp, vp, vp],
         'wbx_ens_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp],
         'wbx_zonal_spectrum': [vp, vp, i64, i64, i64, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp],

@@ -319,7 +319,7 @@ class Aggregator:
     reduce_set = set(self.reduce_dims)
     if not reduce_set <= set(stat.dims):
       return None  # variables without every reduce dim are dropped (aggregation.py:305-309)
-    if isinstance(stat, (lazy.LazyContingency, lazy.LazyEnsProbContingency)) and stat.is_lazy:
+    if isinstance(stat, (lazy.LazyContingency, lazy.LazyEnsProbContingency, lazy.LazyFSS)) and stat.is_lazy:
       fused = self._try_contingency(stat, reduce_set, use_mask, skipna)
       if fused is not None:
         return fused  # (else: `.data` is read below -- the host route)
@@ -564,7 +564,15 @@ class Aggregator:
     w_da, bin_dims = wp
     if lane_dims & set(bin_dims) or (w_da is not None and lane_dims & set(w_da.dims)):
       return None
-    return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
+    if not isinstance(stat, lazy.LazyFSS):
+      return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
+    try:
+      return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
+    except engine.planner.FssPlanError as e:  # latitude kept while the weights depend on a reduced dim: the host route, and said so
+      lazy.FSS_STATS['plan_declined'] += 1
+      if len(lazy.FSS_STATS['reasons']) < 32:
+        lazy.FSS_STATS['reasons'].append(str(e))
+      return None
 
   def _reduce_contingency(self, stat, w_da, bin_dims, use_mask, skipna):
     """One cell of a thresholded contingency table: the four cells of a (p, t) pair are the lane blocks of ONE launch
@@ -580,10 +588,11 @@ class Aggregator:
     values, counts, out_dims = hit
     k, cell = int(np.prod(lane_shape, dtype=np.int64)), stat._cell  # pylint: disable=protected-access
     values, counts = values[cell * k:(cell + 1) * k], counts[cell * k:(cell + 1) * k]
-    if len(lane_shape) > 1:  # (an axis split into the dims it stands for: still a view)
+    if len(lane_shape) != 1:  # (an axis split into the dims it stands for, or dropped where there is none: still a view)
       values, counts = values.reshape(lane_shape + values.shape[1:]), counts.reshape(lane_shape + counts.shape[1:])
     dims_in = lane_dims + tuple(out_dims)
-    final_dims = tuple(d for d in tuple(grp.dims) + lane_dims if d in dims_in) + tuple(bin_dims)
+    # (lazy.LazyFSS says in which order the host route has its dims)
+    final_dims = tuple(d for d in getattr(stat, 'result_dims', tuple(grp.dims) + lane_dims) if d in dims_in) + tuple(bin_dims)
     # (exactly the host route's coordinates: every one whose dims all survive stays, a `mask` among them -- see _aggregate)
     coords = {n: x for n, x in stat._coords.items() if set(x[0]) <= set(final_dims)}  # pylint: disable=protected-access
     if w_da is not None:
@@ -596,8 +605,9 @@ class Aggregator:
     def mk(a):
       a = np.transpose(np.asarray(a, dtype=np.float64), order)  # (a slice of lanes, transposed: still a view)
       # deferred: keep the view of the buffer the GPU is still writing / accumulating -- no reads here
-      return xr.DataArray(a if pending else np.ascontiguousarray(a), dims=final_dims, coords=coords, name=stat.name,
-                          attrs=stat.attrs, _raw_coords=True)
+      # (np.ascontiguousarray would turn a 0-d result -- a scalar neighbourhood size, every dim reduced -- into one of shape (1,))
+      return xr.DataArray(a if pending else (np.ascontiguousarray(a) if a.ndim else np.array(a)), dims=final_dims, coords=coords,
+                          name=stat.name, attrs=stat.attrs, _raw_coords=True)
     return AggregationState(mk(values), mk(counts))
 
   def _reduce_spectrum(self, stat: 'spectra.LazySpectrum', w_da, bin_dims):

@@ -243,6 +243,42 @@ def _device_plan(ctx, plan: planner.S1Plan) -> _PlanOnDevice:
   return _plan_cache[key]
 
 
+class _FssPlanOnDevice:
+  """ctypes wbx_fss_plan + the device copies of its tables."""
+
+  def __init__(self, ctx: _hip.Context, plan: planner.FssPlan):
+    self.keep = []
+    s = _hip.FssPlanStruct()
+    s.nkey, s.ndepth, s.nlat, s.nlon = plan.nkey, plan.ndepth, plan.nlat, plan.nlon
+    s.x_kept, s.nchunk, s.depth_chunk = int(plan.x_kept), plan.nchunk, plan.depth_chunk
+    for i in range(3):
+      s.lat_stride[i], s.lon_stride[i] = plan.lat_stride[i], plan.lon_stride[i]
+      s.key_off[i] = _PlanOnDevice._up(self, ctx, plan.key_off[i])
+      s.depth_off[i] = _PlanOnDevice._up(self, ctx, plan.depth_off[i])
+    s.flags = plan.flags
+    s.wrap_longitude = int(plan.wrap_longitude)
+    self.struct = s
+
+
+_fss_plan_cache: dict = {}
+
+
+def _fss_planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, wrap_longitude):
+  """(the S1Plan stage 2 sees, the device wbx_fss_plan) through a cheap signature, like _planned_inner: steady-state chunks skip
+  table building and uploads.  `layouts` = the engine's four (p, t, -, mask)."""
+  sig = (id(ctx), tuple(dims), tuple(sizes[d] for d in dims),
+         tuple(None if l is None else (tuple(sorted(l.strides.items(), key=str)), l.itemsize) for l in layouts),
+         tuple(sorted(reduce_dims, key=str)), tuple(sorted(wdep, key=str)), flags, bool(wrap_longitude))
+  hit = _fss_plan_cache.get(sig)
+  if hit is None:
+    fplan = planner.build_fss_plan(dims, sizes, [layouts[0], layouts[1], layouts[3]], reduce_dims, wdep_dims=wdep, flags=flags,
+                                   wrap_longitude=wrap_longitude)
+    if len(_fss_plan_cache) > 64:
+      _fss_plan_cache.clear()
+    hit = _fss_plan_cache[sig] = (fplan.s1, _FssPlanOnDevice(ctx, fplan), fplan)
+  return hit[0], hit[1]
+
+
 class _WOnDevice:
   """Stage-2 operand: dense W, or (weights, membership bits) for boolean bin masks."""
 
@@ -528,6 +564,16 @@ def seeps_available(ctx) -> bool:
     return False
 
 
+def fss_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_fss_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_fss_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def new_context() -> _hip.Context:
   """A second context (own HIP stream) on the default device -- the chunk feeder's copy stream."""
   return _hip.Context(_hip.default_context().device_id)
@@ -594,6 +640,7 @@ def clear_caches():
   _plan_cache.clear()
   _w_cache.clear()
   _fast_plan_cache.clear()
+  _fss_plan_cache.clear()
   _count_cache.clear()
   _const_roots.clear()
   _scratch_bufs.clear()
@@ -811,6 +858,7 @@ VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
 IvlArgs = collections.namedtuple('IvlArgs', 'params')  # a HOST array of three _hip.IvlLaneStruct: no device buffer to keep
 SeepsArgs = collections.namedtuple('SeepsArgs', 'dry table cell_stride')
+FssArgs = collections.namedtuple('FssArgs', 'n')
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -968,6 +1016,14 @@ def _seeps_operands(ctx, devs, func, ens, cat, mdim):
   return _hip.SEEPS_LANES, None, SeepsArgs(float(cat['dry_threshold']), buf, int(length))
 
 
+def _fss_operands(ctx, devs, func, ens, cat, mdim):
+  """`cat` = {'n': the neighbourhood size of this launch, 'wrap_longitude'}; raises what the launch would refuse."""
+  n = int(cat['n'])
+  if n < 1 or n % 2 != 1:
+    raise ValueError('neighborhood_size must be odd.')
+  return _hip.FSS_LANES, None, FssArgs(n)
+
+
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
@@ -1012,6 +1068,8 @@ _KINDS = {
                    lambda d, out, dt, func, ens, cat:
                    ('wbx_seeps_partial', (dt, C.c_double(cat.dry), d[0], d[1], d[2], _table_ptr(cat.table), int(cat.cell_stride), d[3],
                                           out))),
+    'fss': _Kind(_fss_operands, (),
+                 lambda d, out, dt, func, ens, cat: ('wbx_fss_partial', (dt, int(cat.n), d[0], d[1], d[3], out))),
 }
 
 
@@ -1734,7 +1792,11 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts}, K * J <= _hip.EPC_MAX_PAIRS; value lane
   cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2) / 'seeps' (SEEPS from a per-place score table,
   wbx_seeps_partial: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table' (float64
-  [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2).
+  [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2) / 'fss' (the three terms of the fractions
+  skill score at ONE neighbourhood size, wbx_fss_partial: inputs (p, t) over one frame with `latitude` and `longitude`, `cat` = {'n',
+  'wrap_longitude'}, `mask` the mask of the statistic for that size; the plan is planner.build_fss_plan's -- x is longitude, latitude
+  is the last key dim whatever the weights depend on, planner.FssPlanError where it cannot be --; value lanes (Pf - Tf)^2, Pf^2, Tf^2;
+  the same stage 2).
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1797,6 +1859,8 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
         x_weights, wdep, w_da = xw, set(), None
       else:
         hit = None
+  if kind == 'fss':  # the stencil's own plan; `plan` is how stage 2 sees its partial (planner.build_fss_plan)
+    hit = _fss_planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, bool(cat.get('wrap_longitude', False)))
   plan, dplan = hit if hit is not None else _planned(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, flags)
   nl, ens_args, cat_args = _KINDS[kind].operands(ctx, devs, func, ens, cat, member_dim)
   counted = bool(flags & 3)

@@ -68,6 +68,15 @@ FUSED_ENS_PROB = os.environ.get('WBX_FUSED_ENS_PROB', '1') != '0'
 # broadcast coefficient fields and a Boolean mask per chunk and variable, reduced as before wbx_seeps_partial existed (A/B timing,
 # tests).
 FUSED_SEEPS = os.environ.get('WBX_FUSED_SEEPS', '1') != '0'
+# False (WBX_FUSED_FSS=0): SquaredFractionsError, SquaredPredictionFraction and SquaredTargetFraction (FSS) each form their
+# neighbourhood means as whole-array float64 running sums per size and hand three float32 fields to the reduction, as before
+# wbx_fss_partial existed (A/B timing, tests).
+FUSED_FSS = os.environ.get('WBX_FUSED_FSS', '1') != '0'
+FSS_TERM = {'SquaredFractionsError': 0, 'SquaredPredictionFraction': 1, 'SquaredTargetFraction': 2}  # value lanes (wbx.h)
+FSS_SIZE_DIM = 'neighborhood_size'
+# reductions of fused FSS statistics that the stencil's plan could not serve and that took the host route instead, with the plan's
+# reasons (tests and tools read these, like replay.STATS)
+FSS_STATS = {'plan_declined': 0, 'reasons': []}
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -221,7 +230,8 @@ class FusedGroup:
     # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}; kinds 'ens2', 'wass': + {'N'}
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
     # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
-    # 'device_tables', 'host', 'mask_da'} (seeps_statistic)
+    # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
+    # per size, or None)} (fss_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -257,7 +267,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc', 'fss'):
       return [self.p, self.t], 0
     if self.kind == 'ivl':
       return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
@@ -281,6 +291,8 @@ class FusedGroup:
     if self.kind == 'seeps':  # the wet thresholds gathered in place like ACC's climatology; the score table addresses their places
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                  skipna=skipna, clim=self.clim, ens=None, cat=self.cat, may_align=False)
+    if self.kind == 'fss':
+      return self._reduce_fss(inputs, reduce_dims, w_da, bin_dims, use_mask, skipna)
     # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
     # group are its own); 'cat', 'cont', 'epc': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
@@ -319,6 +331,23 @@ class FusedGroup:
     return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block])} for k0 in range(0, nthr, block)], launch,
                              lambda parts: np.concatenate([cells(a) for a in parts], axis=1).reshape(
                                  (_hip.CONT_CELLS * nthr,) + parts[0].shape[1:]))
+
+  def _reduce_fss(self, inputs, reduce_dims, w_da, bin_dims, use_mask, skipna):
+    """The three terms of the fractions skill score: one launch per neighbourhood size (wbx_fss_partial; the shared count lane of a
+    mask does not allow several sizes in one), each under the mask of the statistic for ITS size, joined on the host term by term:
+    the result is (3 * K,) + out_dims with lane term * K + k.  A scalar size is one launch and nothing is joined."""
+    cat = self.cat
+    sizes, masks = list(cat['sizes']), cat['masks']
+
+    def launch(k):
+      return engine.reduce_statistics('fss', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims,
+                                      mask=masks[k] if (use_mask and masks is not None) else None, skipna=skipna,
+                                      cat={'n': int(sizes[k]), 'wrap_longitude': bool(cat['wrap_longitude'])})
+    if len(sizes) == 1:
+      return launch(0)
+    nl = _hip.FSS_LANES
+    return _reduce_in_blocks(range(len(sizes)), launch,
+                             lambda parts: np.stack(parts, axis=1).reshape((nl * len(parts),) + parts[0].shape[1:]))
 
   def _reduce_epc(self, launch):
     """Contingency tables of ensemble event probabilities: one launch for up to _hip.EPC_MAX_PAIRS (event threshold k, probability
@@ -792,6 +821,97 @@ class LazyContingency(xr.LazyPickleMixin, xr.DataArray):
   @property
   def dtype(self):
     return np.dtype(np.float32)
+
+
+class LazyFSS(xr.LazyPickleMixin, xr.DataArray):
+  """One term of the fractions skill score -- SquaredFractionsError, SquaredPredictionFraction or SquaredTargetFraction -- of (p, t)
+  at a neighbourhood size, or at several along a leading `neighborhood_size` dim.  The three terms of one (p, t, sizes, wrap,
+  combine_mask) share a FusedGroup of kind 'fss', so the Aggregator gets all of them from one launch per size (wbx_fss_partial).
+  Reading `.data` gives the host route's array (torch stays torch) and needs no device."""
+
+  def __init__(self, group: FusedGroup, term: int, host, mask=None, name=None):
+    cat = group.cat
+    self._data = None
+    rest = tuple(d for d in group.dims if d not in ('latitude', 'longitude'))
+    lead = () if cat['scalar'] else (FSS_SIZE_DIM,)
+    self._dims = lead + rest + ('latitude', 'longitude')  # the host route's order: the spatial dims end up last
+    self.name = name
+    self.attrs = {}
+    self._coords = {k: v for k, v in group.coords.items() if k != 'mask'}
+    if not cat['scalar']:
+      self._coords[FSS_SIZE_DIM] = ((FSS_SIZE_DIM,), np.asarray(list(cat['sizes'])))
+    if mask is not None:  # what _FractionStatistic._compute_per_variable attaches
+      self._coords['mask'] = (tuple(mask.dims), np.asarray(mask.values, dtype=bool))
+    self._group = group
+    self._cell = int(term)
+    self._host = host
+
+  @property
+  def is_lazy(self) -> bool:
+    return self._data is None
+
+  # what the Aggregator's route for lane blocks asks (shared with LazyContingency)
+  @property
+  def lane_dims(self) -> tuple:
+    return () if self._group.cat['scalar'] else (FSS_SIZE_DIM,)
+
+  @property
+  def lane_shape(self) -> tuple:
+    return () if self._group.cat['scalar'] else (len(self._group.cat['sizes']),)
+
+  @property
+  def result_dims(self) -> tuple:
+    return self._dims
+
+  @staticmethod
+  def launchable() -> bool:
+    try:
+      return FUSED_FSS and engine.fss_available(_hip.default_context())
+    except _hip.WbxUnavailableError:
+      return False
+
+  frame = LazyContingency.frame
+
+  @property
+  def data(self):
+    if self._data is None:
+      self._data = self._host().transpose(*self._dims).data
+    return self._data
+
+  @property
+  def shape(self):
+    sizes = dict(self._group.sizes, **{FSS_SIZE_DIM: len(self._group.cat['sizes'])})
+    return tuple(sizes[d] for d in self._dims)
+
+  @property
+  def dtype(self):
+    wide = str(self._group.p.dtype) == 'float64' and 1 in [int(n) for n in self._group.cat['sizes']]
+    return np.dtype(np.float64 if wide else np.float32)
+
+
+def fss_statistic(term: int, p, t, sizes, wrap_longitude: bool, mask, *, combine_mask: bool = False, host=None, name=None) -> xr.DataArray:
+  """Term `term` (FSS_TERM) of the fractions skill score of (p, t) as a LazyFSS.  `sizes`: one odd neighbourhood size or a sequence
+  of them (a leading `neighborhood_size` dim); `mask`: what spatial.get_fss_mask returns for these sizes (a Boolean DataArray, the
+  size dim leading where there are several) or None -- the mask of the STATISTIC, the kernel does not erode masks; `host()`: the host
+  route's DataArray, which whoever reads the per-point values gets.  One group per (p, t, sizes, wrap, combine_mask): the three terms
+  of one FSS meet in it."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  scalar = not isinstance(sizes, (list, tuple, np.ndarray))
+  size_list = [int(sizes)] if scalar else [int(n) for n in sizes]
+  ckey = ('fss', tuple(size_list), scalar, bool(wrap_longitude), bool(combine_mask))
+  grp = _group_for('fss', p, t, clim_key=ckey, cat={'sizes': size_list, 'scalar': scalar, 'wrap_longitude': bool(wrap_longitude),
+                                                     'masks': None})
+  if mask is not None and grp.cat['masks'] is None:  # one DataArray per size: its device copy is cached on the object
+    vals = np.asarray(mask.values, dtype=bool)
+    mdims = tuple(mask.dims)
+    if scalar:
+      grp.cat['masks'] = [xr.DataArray(np.ascontiguousarray(vals), dims=mdims)]
+    else:
+      vals = np.moveaxis(vals, mdims.index(FSS_SIZE_DIM), 0)
+      rest = tuple(d for d in mdims if d != FSS_SIZE_DIM)
+      grp.cat['masks'] = [xr.DataArray(np.ascontiguousarray(vals[k]), dims=rest) for k in range(len(size_list))]
+  return LazyFSS(grp, term, host, mask=mask, name=p.name if name is None else name)
+
 
 
 def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr.DataArray:

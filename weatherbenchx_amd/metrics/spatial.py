@@ -1,8 +1,10 @@
 """Fractions skill score and its neighbourhood averaging (counterpart of weatherbenchX/metrics/spatial.py:24-339).
 
-Outside the path SURVEY section 8 names and without a kernel of its own: the neighbourhood means are sliding-window sums on whatever
-holds the payload (NumPy on the host, torch for a chunk in HBM), the three per-point statistics are squares of them, and their
-weighted, binned, masked means are the Aggregator's reduction like every other statistic.
+Outside the path SURVEY section 8 names.  Under the Aggregator the three per-point statistics of a (predictions, targets) pair are the
+value lanes of one fused launch per neighbourhood size (wbx_fss_partial, `_FractionStatistic._fused`).  The host route, which
+everything the gate declines takes and which whoever reads `.values` gets: the neighbourhood means are sliding-window sums on
+whatever holds the payload (NumPy on the host, torch for a chunk in HBM), the three per-point statistics are squares of them, and
+their weighted, binned, masked means are the Aggregator's reduction like every other statistic.
 
 The reference convolves with `scipy.ndimage.convolve1d` (two passes of n taps per point, field by field through
 `xr.apply_ufunc(vectorize=True)`).  Here a window sum is a difference of two running sums -- independent of n -- over all fields of
@@ -15,6 +17,9 @@ from typing import Iterable, Mapping, Union
 
 import numpy as np
 
+from weatherbenchx_amd import _hip
+from weatherbenchx_amd import engine
+from weatherbenchx_amd import lazy
 from weatherbenchx_amd import xarray_lite as xr
 from weatherbenchx_amd.metrics import base
 
@@ -152,12 +157,68 @@ class _FractionStatistic(base.PerVariableStatistic):
 
   def _compute_per_variable(self, predictions, targets):
     predictions, targets = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+    fused = self._fused(predictions, targets)
+    return fused if fused is not None else self.host_per_variable(predictions, targets)
+
+  def host_per_variable(self, predictions, targets):
     mask = get_fss_mask(predictions, targets, self.neighborhood_size_in_pixels, self.wrap_longitude, self.combine_mask)
     result = self._term(predictions, targets)
     if mask is not None:
       mask = mask.transpose(*[d for d in result.dims if d in mask.dims])
       result._coords['mask'] = (tuple(mask.dims), np.asarray(mask.values, dtype=bool))  # pylint: disable=protected-access
     return result
+
+  def _fused(self, predictions, targets):
+    """This term as a lazy statistic that the Aggregator reduces with wbx_fss_partial (lazy.fss_statistic: the three terms of one
+    (predictions, targets, sizes, wrap_longitude, combine_mask) share their launches, one per size), or None where the host route
+    (`host_per_variable`) has to do it: the switch is off (WBX_FUSED_FSS=0); no device or library, or no such symbol in it;
+    predictions and targets that are not both float32 or both float64 over one frame (equal dims, sizes and labels) that has
+    `latitude` and `longitude`; a longitude stride other than 1 in either as a launch will see it (the row loads of the kernel would
+    not coalesce); more than 2048 longitudes (the circle's prefix lives in LDS); a size that is even (the host route raises, as
+    before), below 1, or larger than the smaller of the two spatial extents.  Two conditions are only known when the statistic is
+    reduced, and the Aggregator then reads `.values`, i.e. takes the host route: a weighting or binning from outside the package, and
+    `latitude` kept while the weights depend on a REDUCED dim -- the one case in which the plan cannot make latitude its last key
+    dim (planner.build_fss_plan); `longitude` is x and can always be kept.  The result has the host route's dims, name and
+    coordinates, its `mask` coordinate among them (computed on the host as before: the kernel does not erode masks), and its
+    `.values` are the host route's."""
+    term = lazy.FSS_TERM.get(type(self).__name__)
+    if not lazy.FUSED_FSS or term is None:
+      return None
+    p, t = predictions, targets
+    dtype = str(p.dtype)
+    if dtype not in ('float32', 'float64') or str(t.dtype) != dtype:
+      return None
+    if set(p.dims) != set(t.dims) or not set(_SPATIAL) <= set(p.dims) or any(p.sizes[d] != t.sizes[d] for d in p.dims):
+      return None
+    for d in p.dims:
+      if (d in p.coords) != (d in t.coords) or (d in p.coords and not xr._values_equal(p.coords[d].values, t.coords[d].values)):  # pylint: disable=protected-access
+        return None
+    sizes = self.neighborhood_size_in_pixels
+    size_list = [sizes] if not isinstance(sizes, Iterable) else list(sizes)
+    if isinstance(sizes, Iterable) and not isinstance(sizes, (list, tuple, np.ndarray)):
+      return None
+    nlat, nlon = int(p.sizes['latitude']), int(p.sizes['longitude'])
+    if not size_list or nlon > _hip.FSS_MAX_NLON:
+      return None
+    for n in size_list:
+      if int(n) != n or n < 1 or n % 2 != 1 or (n > 1 and n > min(nlat, nlon)):
+        return None
+    if lazy.payload_layout(p).stride('longitude') != 1 or lazy.payload_layout(t).stride('longitude') != 1:
+      return None
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+      return None
+    if not engine.fss_available(ctx):
+      return None
+    mask = get_fss_mask(p, t, sizes, self.wrap_longitude, self.combine_mask)
+    lead = (lazy.FSS_SIZE_DIM,) if isinstance(sizes, Iterable) else ()
+    order = lead + tuple(d for d in p.dims if d not in _SPATIAL) + _SPATIAL  # the host route's dims
+    if mask is not None:
+      mask = mask.transpose(*[d for d in order if d in mask.dims])
+    return lazy.fss_statistic(term, p, t, sizes if isinstance(sizes, Iterable) else int(sizes),
+                              self.wrap_longitude, mask, combine_mask=self.combine_mask,
+                              host=lambda: self.host_per_variable(p, t), name=p.name)
 
 
 @dataclasses.dataclass

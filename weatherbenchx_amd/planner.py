@@ -19,6 +19,8 @@ from typing import Sequence
 
 import numpy as np
 
+from weatherbenchx_amd import _hip
+
 MAX_INPUTS = 4
 TARGET_BLOCKS = 4096  # >> 256 CUs * resident blocks, so the tail is short
 # geometry of the flat one-point-per-lane sweep (s1_xf1_kernel): threads per block, fewest elements per block
@@ -340,6 +342,77 @@ def build_s1_plan(dims: Sequence, sizes: dict, layouts: Sequence[InputLayout | N
                 key_off=key_off[:MAX_INPUTS], depth_off=depth_off[:MAX_INPUTS], gather_key=gk, gather_depth=gd,
                 gather_tab=gtab, n_gather_depth=int(ngd), flags=int(flags), block_threads=int(block_threads),
                 vec=int(vec))
+
+# The depth chunking of wbx_fss_partial follows the library's band rule (include/wbx.h; _hip.fss_band_rows halves the band while a
+# launch has fewer than _hip.FSS_TARGET_BLOCKS blocks): depth is cut until a launch would have twice that many blocks at bands of
+# half the largest band, so that the rule has room to settle on either side.  Both numbers derive from the library's own.
+FSS_CHUNKING_BLOCKS = 2 * _hip.FSS_TARGET_BLOCKS
+FSS_CHUNKING_BAND = _hip.FSS_MAX_BAND_ROWS // 2
+FSS_XKEPT_PARTIAL_BYTES = 256 << 20  # the largest x-kept partial the depth chunking of wbx_fss_partial asks for
+
+
+class FssPlanError(ValueError):
+  """The stencil plan cannot keep what the caller keeps (the caller takes the host route)."""
+
+
+@dataclasses.dataclass
+class FssPlan:
+  """Plan of wbx_fss_partial (include/wbx.h: wbx_fss_plan).  Inputs are (p, t, mask); `s1` is how stage 2, the accumulators and
+  the result targets see the partial: the S1Plan of `nkey * nlat` keys with latitude the fastest key index and x = longitude."""
+  s1: S1Plan
+  nkey: int
+  ndepth: int
+  nlat: int
+  nlon: int
+  x_kept: bool
+  nchunk: int
+  depth_chunk: int
+  lat_stride: list
+  lon_stride: list
+  key_off: list    # per input: int64[nkey] or None
+  depth_off: list  # per input: int64[ndepth] or None
+  flags: int
+  wrap_longitude: bool
+
+
+def build_fss_plan(dims: Sequence, sizes: dict, layouts: Sequence[InputLayout | None], reduce_dims, wdep_dims=(), flags: int = 0,
+                   wrap_longitude: bool = False, lat_dim='latitude', lon_dim='longitude',
+                   target_blocks: int = FSS_CHUNKING_BLOCKS) -> FssPlan:
+  """Plans wbx_fss_partial.  `layouts` = (p, t, mask | None).  x is `lon_dim`; `lat_dim` and every dim that is kept or that the
+  weights / bins depend on go into the key, reduced dims the weights do not depend on are depth.  Latitude has to be the LAST key
+  dim (partial_out[nkey][nlat]...): it is whenever it is reduced, or kept with no reduced dim among the weights' dims; otherwise
+  FssPlanError."""
+  dims = tuple(dims)
+  if lat_dim not in dims or lon_dim not in dims:
+    raise FssPlanError(f'the frame {dims} lacks {lat_dim!r} or {lon_dim!r}')
+  order = tuple(d for d in dims if d not in (lat_dim, lon_dim)) + (lat_dim, lon_dim)
+  lays = list(layouts) + [None] * (3 - len(layouts))
+  s1 = build_s1_plan(order, sizes, [lays[0], lays[1], None, lays[2]], reduce_dims, wdep_dims=set(wdep_dims) | {lat_dim}, flags=flags,
+                     allow_vec4=False, force_x_dim=lon_dim)
+  if not s1.key_dims or s1.key_dims[-1] != lat_dim:
+    raise FssPlanError(f'{lat_dim!r} is kept while the weights depend on the reduced dims {s1.br_dims}: it cannot be the last key dim')
+  nlat, nlon = int(s1.sizes[lat_dim]), int(s1.nx)
+  nkey = s1.nkey // nlat if nlat else 0
+  nchunk, depth_chunk = s1.nchunk, s1.depth_chunk
+  if not s1.x_kept:  # a block owns a band of latitudes, not one: chunk the depth for the blocks THIS launch has
+    units = max(nkey, 1) * max(1, -(-nlat // FSS_CHUNKING_BAND))
+    nchunk = int(min(max(s1.ndepth, 1), max(1, -(-target_blocks // units))))
+    depth_chunk = -(-max(s1.ndepth, 1) // nchunk)
+    nchunk = -(-max(s1.ndepth, 1) // depth_chunk)
+    s1 = dataclasses.replace(s1, nchunk=int(nchunk), depth_chunk=int(depth_chunk))
+  elif nlat and nlon:  # x kept: more chunks are more blocks, but every chunk is one more partial of nkey * nlat * lanes * nlon doubles
+    units = max(nkey, 1) * max(1, -(-nlat // FSS_CHUNKING_BAND))
+    per_chunk = max(nkey, 1) * nlat * 6 * nlon * 8
+    nchunk = int(min(max(s1.ndepth, 1), max(1, FSS_XKEPT_PARTIAL_BYTES // per_chunk), max(1, -(-target_blocks // units))))
+    depth_chunk = -(-max(s1.ndepth, 1) // nchunk)
+    nchunk = -(-max(s1.ndepth, 1) // depth_chunk)
+    s1 = dataclasses.replace(s1, nchunk=int(nchunk), depth_chunk=int(depth_chunk))
+  src = (0, 1, 3)  # p, t, mask among the S1Plan's inputs
+  key_off = [None if lay is None else _offset_table(s1.key_dims[:-1], s1.sizes, lay) for lay in lays[:3]]  # (latitude is a stride)
+  return FssPlan(s1=s1, nkey=int(nkey), ndepth=int(s1.ndepth), nlat=nlat, nlon=nlon, x_kept=bool(s1.x_kept), nchunk=int(nchunk),
+                 depth_chunk=int(depth_chunk), lat_stride=[0 if lays[j] is None else lays[j].stride(lat_dim) for j in range(3)],
+                 lon_stride=[int(s1.xstride[i]) for i in src], key_off=key_off, depth_off=[s1.depth_off[i] for i in src],
+                 flags=int(flags), wrap_longitude=bool(wrap_longitude))
 
 
 @dataclasses.dataclass
