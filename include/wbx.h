@@ -583,6 +583,43 @@ int wbx_ens_prob_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int 
                                      const int32_t* slots /* DEVICE int32[2 * nslot]: lo, hi */, const void* p, const void* t,
                                      const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: Brier-type errors of event probabilities (joined ABI 13) -----------------------------------------------
+ * Error, AbsoluteError and SquaredError (deterministic.py:91-123) of an event probability against the observed event, behind
+ * ContinuousToBinary('both', event thresholds) -> EnsembleMean('predictions') or WeibullEnsembleToProbabilistic('predictions')
+ * (wrappers.py): Bias, MAE and MSE / RMSE -- the Brier score -- per threshold, in one pass over p and t: no [nthr][M][frame]
+ * indicator array is formed.  p has a member axis of length M and element stride `member_stride` that is not part of key / depth /
+ * x, as for wbx_ens_partial.  M == 1 is the deterministic pair behind the first transform alone: `member_stride` is then ignored
+ * and `denom` must be 1.
+ * Per point, with members x_m (m < M), target y, thresholds a_k = thresholds[k] and D = denom (M: the member mean; M + 1: Weibull's
+ * plotting position):
+ *     c_k = #{m : (double)x_m > a_k}     o_k = [(double)y > a_k]     e_k = c_k - o_k * D        (strict, on the threshold as given)
+ *     lane ERR * nthr + k : e_k / D      lane ABS * nthr + k : |e_k| / D      lane SQ * nthr + k : e_k^2 / D^2
+ * Lane order is part of the ABI: WBX_BRIER_STATS * nthr value lanes, stat * nthr + k, stat in (ERR, ABS, SQ) = (0, 1, 2).
+ * A comparison with a NaN threshold is false; -0.0 > 0.0 is false; +-inf compare as IEEE says.  float32 inputs are compared in
+ * float32 against the threshold rounded toward -inf to float32, exactly as in wbx_contingency_partial.
+ * No floating-point number is added anywhere and nothing is added atomically.  A partial is the signed 64-bit sum S of the integer
+ * numerators e_k, |e_k| or e_k^2 over its points, written once as (double)S / (double)D (ERR, ABS) or (double)S / (double)(D * D)
+ * (SQ): every written value is the correctly rounded quotient of two integers, a function of the inputs and the plan only, bit for
+ * bit, in any summation order.
+ * A point with a NaN member or a NaN target is a NaN statistic in all 3 * nthr lanes: without flags it poisons every value lane of
+ * its partial; under WBX_FLAG_MASKED alone it contributes exactly 0 where the mask is 0 and poisons where it is not; under
+ * WBX_FLAG_SKIPNA it is counted out.  Count lanes follow the library's convention (none / one shared / one per value lane); under
+ * SKIPNA all of them are equal (the number of valid, non-NaN points).  partial_out[nkey][nchunk][lanes_total][nj] as for
+ * wbx_det_partial: wbx_s1_partial_len with lanes = 3 * nthr; wbx_contract, wbx_contract_bits, the accumulators and the chunk records
+ * take it unchanged.
+ * Refused (WBX_ERR_INVALID, output untouched): nthr outside 1..WBX_BRIER_MAX_THRESHOLDS, M outside 1..WBX_BRIER_MAX_MEMBERS, denom
+ * not in {M, M + 1} (not 1 when M == 1), an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask,
+ * plane_rows != 0 or x_weights, a NULL threshold table, and depth_chunk * nx * denom^2 >= 2^53 (S must stay exact in fp64).
+ * vec = 4 is accepted and read with dword loads (a lane owns a point and walks its members).  nkey == 0 touches nothing;
+ * ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_BRIER_STATS 3            /* ERR, ABS, SQ */
+#define WBX_BRIER_MAX_THRESHOLDS 16  /* per launch */
+#define WBX_BRIER_MAX_MEMBERS 256    /* e_k^2 <= (M + 1)^2 fits an int32 */
+int wbx_ens_brier_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M, int64_t member_stride,
+                          int denom /* M: EnsembleMean; M + 1: Weibull plotting position */, int nthr,
+                          const double* thresholds /* DEVICE float64[nthr] */, const void* p, const void* t, const uint8_t* mask,
+                          double* partial_out);
+
 /* ---- stage 1: SEEPS from a per-place score table (joined ABI 13) ----------------------------------------------------
  * The stable equitable error in probability space (categorical.py:104-304) of a prediction p against a target t: both are put
  * into a category against the dry threshold and the point's climatological wet threshold, and the pair of categories picks one of
@@ -908,7 +945,8 @@ typedef enum wbx_fn {
   WBX_FN_MEMSET = 15, WBX_FN_MEMCPY_D2D = 16, WBX_FN_CTX_WAIT_FENCE = 17, WBX_FN_FENCE_RECORD = 18, WBX_FN_DET_SPECTRUM_FOLDED = 19,
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
-  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28
+  WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28,
+  WBX_FN_ENS_BRIER_PARTIAL = 29
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -39,6 +39,9 @@ IVL_MAX_MEMBERS = 64  # (WBX_IVL_MAX_MEMBERS)
 EPC_CELLS = 4  # wbx_ens_prob_contingency_partial: value lane cell * (nthr * nslot) + k * nslot + j, cell in (TP, FP, FN, TN)
 EPC_MAX_PAIRS = 16  # (event threshold, probability slot) pairs per launch (WBX_EPC_MAX_PAIRS)
 EPC_MAX_MEMBERS = 256  # (WBX_EPC_MAX_MEMBERS)
+BRIER_STATS = 3  # wbx_ens_brier_partial: value lane stat * nthr + k, stat in (ERR, ABS, SQ) (WBX_BRIER_STATS)
+BRIER_MAX_THRESHOLDS = 16  # per launch (WBX_BRIER_MAX_THRESHOLDS)
+BRIER_MAX_MEMBERS = 256  # (WBX_BRIER_MAX_MEMBERS)
 SEEPS_LANES = 1  # wbx_seeps_partial (WBX_SEEPS_LANES)
 SEEPS_CELLS = 9  # cells of its score table: 3 * (category of p) + (category of t) (WBX_SEEPS_CELLS)
 FSS_LANES = 3  # wbx_fss_partial: (Pf - Tf)^2, Pf^2, Tf^2 (WBX_FSS_LANES)
@@ -66,7 +69,7 @@ EXPORTED_SYMBOLS = (
     'wbx_ens2_partial', 'wbx_cat_exceed_field', 'wbx_chunk_replay', 'wbx_host_transpose', 'wbx_clock_probe', 'wbx_det_spectrum_folded',
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
-    'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial',
+    'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial', 'wbx_ens_brier_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -76,7 +79,8 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_memset': 15, 'wbx_memcpy_d2d': 16, 'wbx_ctx_wait_fence': 17, 'wbx_fence_record': 18, 'wbx_det_spectrum_folded': 19,
           'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
           'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25,
-          'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28}
+          'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28,
+          'wbx_ens_brier_partial': 29}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -272,6 +276,7 @@ def load_library():
         'wbx_ens_variogram_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, i32, vp, vp, vp, vp],
         'wbx_ens_wasserstein_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i64, vp, vp, vp, vp],
         'wbx_ens_prob_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, i32, vp, vp, vp, vp, vp],
+        'wbx_ens_brier_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp, vp, vp],
         'wbx_ens_interval_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlLaneStruct), vp, vp, vp, vp, vp],
         'wbx_seeps_partial': [vp, C.POINTER(S1PlanStruct), i32, C.c_double, vp, vp, vp, vp, i64, vp, vp],
         'wbx_fss_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, vp, vp, vp, vp],

@@ -319,7 +319,7 @@ class Aggregator:
     reduce_set = set(self.reduce_dims)
     if not reduce_set <= set(stat.dims):
       return None  # variables without every reduce dim are dropped (aggregation.py:305-309)
-    if isinstance(stat, (lazy.LazyContingency, lazy.LazyEnsProbContingency, lazy.LazyFSS)) and stat.is_lazy:
+    if isinstance(stat, (lazy.LazyContingency, lazy.LazyEnsProbContingency, lazy.LazyFSS, lazy.LazyBrier)) and stat.is_lazy:
       fused = self._try_contingency(stat, reduce_set, use_mask, skipna)
       if fused is not None:
         return fused  # (else: `.data` is read below -- the host route)

@@ -1,4 +1,4 @@
-// The exceedance threshold of the integer-count kernels that compare with a strict `>` (wbx_contingency.hip, wbx_ens_prob.hip).
+// The exceedance threshold of the integer-count kernels that compare with a strict `>` (wbx_contingency.hip, wbx_ens_prob.hip, wbx_ens_brier.hip).
 #pragma once
 #include <cmath>
 #include <type_traits>

@@ -554,6 +554,16 @@ def ens_prob_available(ctx) -> bool:
     return False
 
 
+def brier_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_brier_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_brier_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def seeps_available(ctx) -> bool:
   """Whether `ctx` can launch wbx_seeps_partial (see contingency_available)."""
   if not isinstance(ctx, _hip.Context):
@@ -853,6 +863,7 @@ CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
 EpcArgs = collections.namedtuple('EpcArgs', 'nthr thr nslot slots')
+BrierEnsArgs = collections.namedtuple('BrierEnsArgs', 'm mstride denom')
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
 VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
@@ -898,6 +909,21 @@ def _epc_operands(ctx, devs, func, ens, cat, mdim):
     raise ValueError(f"one launch takes 1..{_hip.EPC_MAX_MEMBERS} members (got {ens['M']})")
   return _hip.EPC_CELLS * nthr * nslot, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), EpcArgs(
       nthr, _threshold_table(ctx, thr), nslot, _slot_table(ctx, slots))
+
+
+def _brier_operands(ctx, devs, func, ens, cat, mdim):
+  """`ens` = {'member_dim', 'M', 'fair': False} or None (a deterministic pair: M = 1), `cat` = {'thresholds', 'denom'}."""
+  thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
+  nthr, m, denom = int(thr.size), int(ens['M']) if ens else 1, int(cat['denom'])
+  if not 1 <= nthr <= _hip.BRIER_MAX_THRESHOLDS:
+    raise ValueError(f'one Brier launch takes 1..{_hip.BRIER_MAX_THRESHOLDS} thresholds (got {nthr})')
+  if not 1 <= m <= _hip.BRIER_MAX_MEMBERS:
+    raise ValueError(f'one Brier launch takes 1..{_hip.BRIER_MAX_MEMBERS} members (got {m})')
+  if denom != 1 if (mdim is None or m == 1) else denom not in (m, m + 1):
+    raise ValueError(f'the denominator of a Brier launch is M or M + 1, and 1 for one member or none (got {denom} for M = {m})')
+  if mdim is None:  # one "member": the entry ignores the stride
+    return _hip.BRIER_STATS * nthr, BrierEnsArgs(1, 0, 1), ContArgs(nthr, _threshold_table(ctx, thr))
+  return _hip.BRIER_STATS * nthr, BrierEnsArgs(m, devs[0].layout.stride(mdim), denom), ContArgs(nthr, _threshold_table(ctx, thr))
 
 
 def norm_run(layout, dims, sizes):
@@ -1055,6 +1081,9 @@ _KINDS = {
                  lambda d, out, dt, func, ens, cat:
                  ('wbx_ens_prob_contingency_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), int(cat.nslot),
                                                        _table_ptr(cat.slots), d[0], d[1], d[3], out))),
+    'brier': _Kind(_brier_operands, ('thr',),
+                   lambda d, out, dt, func, ens, cat:
+                   ('wbx_ens_brier_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), d[0], d[1], d[3], out))),
     'enrg': _Kind(_enrg_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
     'vgrm': _Kind(_vgrm_operands, (),
@@ -1790,7 +1819,10 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   stage 2) / 'epc' (contingency tables of ensemble event probabilities, wbx_ens_prob_contingency_partial: the operands of 'erps' --
   `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag)} --, `cat` = {'thresholds': float64 ndarray of K event
   thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts}, K * J <= _hip.EPC_MAX_PAIRS; value lane
-  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2) / 'seeps' (SEEPS from a per-place score table,
+  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2) / 'brier' (Error, AbsoluteError and SquaredError of event
+  probabilities, wbx_ens_brier_partial: `ens` = {'member_dim', 'M', 'fair': False} or None for a deterministic pair, `cat` =
+  {'thresholds': float64 ndarray of at most _hip.BRIER_MAX_THRESHOLDS, 'denom': M or M + 1, 1 without a member dim}; value lane
+  stat * K + k, stat in (Error, AbsoluteError, SquaredError); the same stage 2) / 'seeps' (SEEPS from a per-place score table,
   wbx_seeps_partial: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table' (float64
   [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2) / 'fss' (the three terms of the fractions
   skill score at ONE neighbourhood size, wbx_fss_partial: inputs (p, t) over one frame with `latitude` and `longitude`, `cat` = {'n',

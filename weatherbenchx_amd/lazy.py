@@ -77,6 +77,11 @@ FSS_SIZE_DIM = 'neighborhood_size'
 # reductions of fused FSS statistics that the stencil's plan could not serve and that took the host route instead, with the plan's
 # reasons (tests and tools read these, like replay.STATS)
 FSS_STATS = {'plan_declined': 0, 'reasons': []}
+# False (WBX_FUSED_BRIER=0): Error, AbsoluteError and SquaredError behind ContinuousToBinary('both') [-> EnsembleMean /
+# WeibullEnsembleToProbabilistic('predictions')] (the Brier score and its kin) build the [K, M, frame] indicator arrays on the host
+# and reduce them as before wbx_ens_brier_partial existed (A/B timing, tests).
+FUSED_BRIER = os.environ.get('WBX_FUSED_BRIER', '1') != '0'
+BRIER_STAT = {'Error': 0, 'AbsoluteError': 1, 'SquaredError': 2}  # lane blocks (wbx.h)
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -231,7 +236,7 @@ class FusedGroup:
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
     # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
     # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
-    # per size, or None)} (fss_statistic)
+    # per size, or None)} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -267,7 +272,7 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc', 'fss'):
+    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc', 'fss', 'brier'):
       return [self.p, self.t], 0
     if self.kind == 'ivl':
       return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
@@ -294,13 +299,15 @@ class FusedGroup:
     if self.kind == 'fss':
       return self._reduce_fss(inputs, reduce_dims, w_da, bin_dims, use_mask, skipna)
     # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
-    # group are its own); 'cat', 'cont', 'epc': one per block
+    # group are its own); 'cat', 'cont', 'epc', 'brier': one per block
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
                                                   skipna=skipna, ens=self.ens, cat=cat)
     if self.kind == 'cat':
       return self._reduce_cat(launch, mask, skipna)
     if self.kind == 'epc':
       return self._reduce_epc(launch)
+    if self.kind == 'brier':
+      return self._reduce_brier(launch)
     return self._reduce_cont(launch) if self.kind == 'cont' else launch(self.cat)
 
   def _reduce_cat(self, launch, mask, skipna):
@@ -331,6 +338,20 @@ class FusedGroup:
     return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block])} for k0 in range(0, nthr, block)], launch,
                              lambda parts: np.concatenate([cells(a) for a in parts], axis=1).reshape(
                                  (_hip.CONT_CELLS * nthr,) + parts[0].shape[1:]))
+
+  def _reduce_brier(self, launch):
+    """Error, AbsoluteError and SquaredError of event probabilities: one launch for up to _hip.BRIER_MAX_THRESHOLDS thresholds; more
+    are cut into blocks -- thresholds are independent of one another --, one launch each, joined on the host statistic by
+    statistic: the result is (3 * K,) + out_dims with lane stat * K + k whatever the number of launches."""
+    thr = np.asarray(self.cat['thresholds'], np.float64)
+    nthr, block, ns, denom = int(thr.size), _hip.BRIER_MAX_THRESHOLDS, _hip.BRIER_STATS, int(self.cat['denom'])
+    if nthr <= block:
+      return launch({'thresholds': thr, 'denom': denom})
+    # (stat, k of the block) + out_dims; the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from
+    stats = lambda a: a.reshape((ns, a.shape[0] // ns) + a.shape[1:])
+    return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block]), 'denom': denom} for k0 in range(0, nthr, block)],
+                             launch, lambda parts: np.concatenate([stats(a) for a in parts], axis=1).reshape(
+                                 (ns * nthr,) + parts[0].shape[1:]))
 
   def _reduce_fss(self, inputs, reduce_dims, w_da, bin_dims, use_mask, skipna):
     """The three terms of the fractions skill score: one launch per neighbourhood size (wbx_fss_partial; the shared count lane of a
@@ -821,6 +842,93 @@ class LazyContingency(xr.LazyPickleMixin, xr.DataArray):
   @property
   def dtype(self):
     return np.dtype(np.float32)
+
+
+class LazyBrier(xr.LazyPickleMixin, xr.DataArray):
+  """Error, AbsoluteError or SquaredError of (the fraction of members over a threshold, or the indicator of a deterministic
+  prediction) against (the target is over that threshold) along a new trailing `threshold_dim`: what these statistics are behind
+  ContinuousToBinary('both') [-> EnsembleMean / WeibullEnsembleToProbabilistic('predictions')].  The three statistics of one (p, t)
+  pair, threshold list, member dim and denominator share a FusedGroup of kind 'brier', so the Aggregator gets all of them from one
+  launch (wbx_ens_brier_partial).  Reading `.data` runs the transforms and the statistic as labelled-array arithmetic on the host,
+  the unfused route's float32 indicator arithmetic, and needs no device."""
+
+  def __init__(self, group: FusedGroup, stat: int, name=None):
+    cat = group.cat
+    self._data = None
+    self._threshold_dim = cat['threshold_dim']
+    self._dims = tuple(group.dims) + (self._threshold_dim,)
+    self.name = name
+    self.attrs = {}
+    self._coords = dict(group.coords)
+    self._coords[self._threshold_dim] = ((self._threshold_dim,), np.asarray(cat['coord']))
+    self._group = group
+    self._cell = int(stat)
+
+  @property
+  def is_lazy(self) -> bool:
+    return self._data is None
+
+  # what the Aggregator's route for lane blocks asks (shared with LazyContingency)
+  @property
+  def lane_dims(self) -> tuple:
+    return (self._threshold_dim,)
+
+  @property
+  def lane_shape(self) -> tuple:
+    return (int(np.asarray(self._group.cat['thresholds']).size),)
+
+  @staticmethod
+  def launchable() -> bool:
+    try:
+      return FUSED_BRIER and engine.brier_available(_hip.default_context())
+    except _hip.WbxUnavailableError:
+      return False
+
+  frame = LazyContingency.frame
+
+  @property
+  def data(self):
+    if self._data is None:
+      from weatherbenchx_amd.metrics import wrappers  # pylint: disable=g-import-not-at-top
+      grp, cat = self._group, self._group.cat
+      pb = wrappers.binarize_thresholds(grp.p, list(cat['values']), self._threshold_dim)
+      tb = wrappers.binarize_thresholds(grp.t, list(cat['values']), self._threshold_dim)
+      if grp.ens is not None:  # the member mean, or Weibull's plotting position (wrappers.WeibullEnsembleToProbabilistic)
+        e, m = grp.ens['member_dim'], int(grp.ens['M'])
+        pb = pb.mean(e, skipna=False) if cat['denom'] == m else pb.sum(e, skipna=False) / (m + 1)
+      d = pb - tb
+      out = (d, abs(d), d ** 2)[self._cell]
+      self._data = out.transpose(*self._dims).data
+    return self._data
+
+  @property
+  def shape(self):
+    return tuple(self._group.sizes[d] for d in self._group.dims) + self.lane_shape
+
+  @property
+  def dtype(self):
+    return np.dtype(np.float32)
+
+
+def brier_statistic(stat: str, p, t, ensemble_dim, threshold_dim: str, thresholds, denom: int) -> xr.DataArray:
+  """`stat` ('Error', 'AbsoluteError', 'SquaredError') of the event probabilities of `p` against the events of `t` as a LazyBrier.
+  `ensemble_dim`: the member dim of `p`, or None for a deterministic pair (`denom` = 1); `thresholds`: the plain sequence of real
+  numbers the ContinuousToBinary was built with; `denom`: M (the member mean) or M + 1 (Weibull's plotting position).  The (p, t)
+  objects, the thresholds' bytes, the member dim and `denom` key the group, so the three statistics of a pair meet in one group."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if ensemble_dim is not None and (ensemble_dim not in p.dims or ensemble_dim in t.dims):
+    raise ValueError(f'{ensemble_dim!r} must be a dim of the predictions and not of the targets')
+  if threshold_dim in p.dims or threshold_dim in t.dims:
+    raise ValueError(f'{threshold_dim!r} is already a dimension of the inputs')
+  values = list(thresholds)
+  thr = np.asarray(values, np.float64).reshape(-1)
+  ckey = ('brier', threshold_dim, thr.tobytes(), int(denom))
+  if not _group_known(p, t, 'brier', lambda k: k[3] == ensemble_dim and k[4] == ckey):
+    p, t = _aligned(p, t)
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': False} if ensemble_dim is not None else None
+  cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim, 'denom': int(denom)}
+  grp = _group_for('brier', p, t, ens=ens, clim_key=ckey, cat=cat)
+  return LazyBrier(grp, BRIER_STAT[stat], name=p.name)
 
 
 class LazyFSS(xr.LazyPickleMixin, xr.DataArray):

@@ -76,25 +76,100 @@ class RelativeIntensity(base.PerVariableStatistic):
     return result
 
 
-class Error(base.PerVariableStatistic):
+def _fused_brier(stat, transforms, predictions, targets):
+  """`stat` (Error, AbsoluteError or SquaredError) behind `transforms`, outermost first, as lazy statistics on the continuous inputs
+  (one fused launch for the three statistics of a variable, lazy.brier_statistic), or None: the caller then transforms and computes
+  as usual.  Two forms are taken:
+    (ContinuousToBinary('both', [numbers], dim),)  around a deterministic pair: no ensemble dim, the denominator is 1;
+    (ContinuousToBinary('both', [numbers], dim), mean)  with `mean` exactly EnsembleMean('predictions', e, skipna=False) (the
+      denominator is M) or WeibullEnsembleToProbabilistic('predictions', e, skipna=False) (M + 1).
+  None for any other chain or `which`, skipna=True, labelled thresholds, an ensemble dim on the targets or none on the predictions
+  (chain form), a dim of the predictions that the targets lack (single-transform form: such a dim is an ensemble dim, and the
+  statistics per member keep the host route), the threshold dim already on an input or equal to the ensemble dim, target dims that
+  are not a subset of the prediction dims, dtypes other than float32 / float64, more than _hip.BRIER_MAX_MEMBERS members, one member
+  under the plotting position, no device, no entry point, the switch off.  The gate never raises: where the host route would, it
+  does."""
+  from weatherbenchx_amd import engine  # pylint: disable=g-import-not-at-top
+  from weatherbenchx_amd.metrics import wrappers  # pylint: disable=g-import-not-at-top
+  if not lazy.FUSED_BRIER or type(stat) not in _BRIER_STATS or len(transforms) not in (1, 2):  # pylint: disable=unidiomatic-typecheck
+    return None
+  outer = transforms[0]
+  if type(outer) is not wrappers.ContinuousToBinary or outer.which != 'both':  # pylint: disable=unidiomatic-typecheck
+    return None
+  values = wrappers.plain_thresholds(outer._threshold_value)  # pylint: disable=protected-access
+  dim = outer._threshold_dim  # pylint: disable=protected-access
+  if values is None:
+    return None
+  e, plotting = None, False
+  if len(transforms) == 2:
+    mean = transforms[1]
+    if type(mean) not in (wrappers.EnsembleMean, wrappers.WeibullEnsembleToProbabilistic):  # pylint: disable=unidiomatic-typecheck
+      return None
+    if mean.which != 'predictions' or mean._skipna:  # pylint: disable=protected-access
+      return None
+    e, plotting = mean._ensemble_dim, type(mean) is wrappers.WeibullEnsembleToProbabilistic  # pylint: disable=protected-access,unidiomatic-typecheck
+    if e == dim:
+      return None
+  pairs = {}
+  for name in predictions.keys():
+    if name not in targets.keys():
+      continue
+    p, t = base._named(predictions[name], name), base._named(targets[name], name)  # pylint: disable=protected-access
+    if (dim in p.dims or dim in t.dims or not set(t.dims) <= set(p.dims)
+        or str(p.dtype) not in ('float32', 'float64') or str(t.dtype) not in ('float32', 'float64')):
+      return None
+    if e is None:
+      if not set(p.dims) <= set(t.dims):
+        return None
+      denom = 1
+    else:
+      if e not in p.dims or e in t.dims or not 1 <= p.sizes[e] <= _hip.BRIER_MAX_MEMBERS:
+        return None
+      denom = p.sizes[e] + 1 if plotting else p.sizes[e]
+      if p.sizes[e] == 1 and denom != 1:
+        return None
+    pairs[name] = (p, t, denom)
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on (the host route says so where it needs one)
+    return None
+  if not engine.brier_available(ctx):
+    return None
+  return {name: lazy.brier_statistic(type(stat).__name__, p, t, e, dim, values, denom) for name, (p, t, denom) in pairs.items()}
+
+
+class _BrierGates:
+  """What wrappers.WrappedStatistic asks a statistic that may know a fused form of itself behind its transforms (_fused_brier)."""
+
+  def compute_with_transform(self, transform, predictions, targets):
+    return _fused_brier(self, (transform,), predictions, targets)
+
+  def compute_with_chain(self, transforms, predictions, targets):
+    return _fused_brier(self, tuple(transforms), predictions, targets) if len(transforms) == 2 else None
+
+
+class Error(_BrierGates, base.PerVariableStatistic):
   """predictions - targets (deterministic.py:91-100)."""
 
   def _compute_per_variable(self, predictions, targets):
     return lazy.det_statistic('Error', predictions, targets)
 
 
-class AbsoluteError(base.PerVariableStatistic):
+class AbsoluteError(_BrierGates, base.PerVariableStatistic):
   """|predictions - targets| (deterministic.py:103-112)."""
 
   def _compute_per_variable(self, predictions, targets):
     return lazy.det_statistic('AbsoluteError', predictions, targets)
 
 
-class SquaredError(base.PerVariableStatistic):
+class SquaredError(_BrierGates, base.PerVariableStatistic):
   """(predictions - targets)**2 (deterministic.py:115-123)."""
 
   def _compute_per_variable(self, predictions, targets):
     return lazy.det_statistic('SquaredError', predictions, targets)
+
+
+_BRIER_STATS = (Error, AbsoluteError, SquaredError)  # exactly these: a subclass may compute something else
 
 
 class PredictionPassthrough(base.PerVariableStatistic):

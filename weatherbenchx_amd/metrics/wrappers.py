@@ -91,6 +91,14 @@ class WrappedStatistic(base.Statistic):
         out = fused((self.transform, mid.transform, mid.statistic.transform), predictions, targets)
         if out is not None:
           return out
+    # ... or behind this wrapper and the one inside it, when this is the outermost of exactly two (deterministic.Error /
+    # AbsoluteError / SquaredError behind ContinuousToBinary('both') -> EnsembleMean / WeibullEnsembleToProbabilistic)
+    elif type(mid) is WrappedStatistic:  # pylint: disable=unidiomatic-typecheck
+      fused = getattr(mid.statistic, 'compute_with_chain', None)
+      if fused is not None:
+        out = fused((self.transform, mid.transform), predictions, targets)
+        if out is not None:
+          return out
     if self.transform.which in ('predictions', 'both'):
       predictions = xarray_tree.map_structure(self.transform.transform_fn, _as_tree(predictions))
     if self.transform.which in ('targets', 'both'):
