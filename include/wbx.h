@@ -59,6 +59,19 @@ typedef enum wbx_dtype { WBX_F32 = 0, WBX_F64 = 1 } wbx_dtype;
  *           the plan's gather table (metrics/base.py:382-406 `.sel(dayofyear,hour)`)
  * WBX_PASS1 input (p):       p          (any already-materialised statistic;
  *           replaces the xr.dot of aggregation.py:335 for user-defined stats)
+ * Accuracy, per output of wbx_det_partial against the exact sum of the exact lane values of the widened inputs: the inputs are
+ * widened to float64 exactly, a lane value carries at most 3 roundings and the N terms of a partial are summed in float64 in a fixed
+ * order (fused multiply-adds where x_weights are folded in), so |error| <= (N + 3) 2^-53 sum |term|, the weights included in the
+ * terms, N = the points of the partial.  Inputs whose terms and partial sums are exact in float64 (small integers, weights k / 8)
+ * give the same bits on every route: s1_xr with vec 1 / vec 4 / the mask row in LDS, s1_xk, plane mode, the flat x-weighted sweep.
+ * Count lanes without x_weights are exact integers.  wbx_det_map: the lane value itself, at most 3 roundings.
+ * Values that are not finite follow IEEE arithmetic of the formulas: without flags a NaN input makes the value lanes that read it
+ * NaN in its own partial (its key, chunk and, where x is kept, x) and in no other; an infinite input gives +-inf there, NaN where
+ * opposite infinities meet.  Under WBX_FLAG_MASKED a point whose mask byte is 0 contributes exactly 0 to every lane whatever it
+ * holds, NaN and infinities included, and a count lane is never NaN.  Under WBX_FLAG_SKIPNA a NaN lane value is left out of its
+ * own lane's sum and count (a NaN climatology alone drops lanes 3-5 of the point and keeps 0-2; a lane without a counted point
+ * has sum 0 and count 0); an infinite lane value is kept.  tests/test_gpu_det_partial.py holds every line of this paragraph
+ * output by output, on every kernel the dispatch can take, against the float64 restatement of tests/det_partial_cases.py.
  */
 typedef enum wbx_det_func { WBX_DET3 = 0, WBX_DET6 = 1, WBX_PASS1 = 2 } wbx_det_func;
 #define WBX_DET3_LANES 3
@@ -157,7 +170,8 @@ typedef struct wbx_s1_plan {
                               take the weight too.  Always with plane_rows = R > 0 (R contiguous depth rows form one span,
                               ndepth % R == 0) and fp32 inputs.  wbx_det_partial (no flag, or WBX_FLAG_MASKED with a mask
                               stored like the data): R % 4 == 0, 16-B aligned spans streamed as one flat float4 array
-                              (element e takes x_weights[e mod nx]), depth_chunk % 4 == 0, nx <= 2045.  wbx_ens_partial
+                              (element e takes x_weights[e mod nx]), depth_chunk % 4 == 0, 1 <= nx <= 2045 (at nx < 4 a float4
+                              spans several whole rows; no lower bound).  wbx_ens_partial
                               (any of FAIR / MASKED / SKIPNA, not SKIPNA_ENS): one point per lane walks the flat index,
                               any R, nx <= 2048. */
 } wbx_s1_plan;

@@ -542,7 +542,8 @@ __global__ void __launch_bounds__(256) s1_xf_kernel(S1Args a, int R) {
   const int64_t d0 = (int64_t)chunk * a.dchunk;
   const int64_t d1 = d0 + a.dchunk < a.D ? d0 + a.dchunk : a.D;
   const int nt = blockDim.x, nwave = nt >> 6;
-  for (int i = tid; i < nx + 3; i += nt) wbx_xw_lds[i] = a.xw[i < nx ? i : i - nx];
+  // (the 3-element pad wraps more than once where nx < 3: a float4 then spans two or more whole rows)
+  for (int i = tid; i < nx + 3; i += nt) wbx_xw_lds[i] = a.xw[i < nx ? i : (i - nx) % nx];
   __syncthreads();
 
   int64_t kb[WBX_MAX_INPUTS];
