@@ -738,6 +738,39 @@ typedef struct wbx_fss_plan {
 int wbx_fss_partial(wbx_ctx* ctx, const wbx_fss_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int n, const void* p, const void* t,
                     const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: the FSS terms of thresholded continuous fields (joined ABI 13) -------------------------------------------
+ * What FSS is scored on in practice: WrappedMetric(FSS(sizes), [ContinuousToBinary('both', thresholds, dim)]) on a continuous field.
+ * The entry takes the CONTINUOUS p and t and the thresholds and forms no indicator field: one call reads p and t once per block of
+ * thresholds (see "Launches") instead of once per threshold, and every window sum is an integer count.
+ * The plan, its strides, tables and flags, the mask's meaning (the mask of the statistic for this size; it has no threshold axis and
+ * serves every threshold), the border rule and wrap_longitude are exactly those of wbx_fss_partial.  The threshold is a LANE, not a
+ * plan dim.
+ * Per point (y, x) and threshold k, a_k = thresholds[k], n odd and greater than 1:
+ *     a member v of a window exceeds a_k where (double)v > a_k -- the host route's float64 comparison.  float32 inputs are compared in
+ *     float32 against a_k rounded toward -inf to float32, which is the same predicate (wbx_contingency_partial words it in full);
+ *     a NaN threshold is never exceeded; -0.0 > 0.0 is false.  +-inf inputs are ORDINARY numbers here (+inf exceeds every threshold
+ *     but +inf and NaN, -inf exceeds none) -- unlike wbx_fss_partial, whose float64 running sums put them outside its contract
+ *     C_p,k = the number of members of p's n x n window (longitude cyclic) that exceed a_k;   H_p = the number of NaN members, which
+ *     does not depend on k;   C_t,k, H_t the same from t
+ *     Pf = (float)((double)C_p,k / (double)(n * n)), or NaN where H_p > 0, and 0 at border points whatever the window holds; Tf alike
+ *     value lanes, formed in float32, then widened:  3 k + 0 (Pf - Tf)^2,  3 k + 1 Pf^2,  3 k + 2 Tf^2
+ * n == 1: Pf is the indicator itself -- 0, 1, or NaN where the point is NaN -- and there is no border.
+ * partial_out[nkey][nlat][nchunk][lanes_total][nj] with 3 * nthr value lanes and the library's count lanes behind them: none; ONE
+ * shared lane (3 * nthr) under WBX_FLAG_MASKED alone; one per value lane (3 * nthr + 3 k + l) under WBX_FLAG_SKIPNA.  Hence lanes_total
+ * is 3 nthr, 3 nthr + 1 or 6 nthr; wbx_s1_partial_len (lanes = 3 * nthr), wbx_contract and wbx_contract_bits serve it unchanged.
+ * Sums.  For every k, lanes 3 k .. 3 k + 2 and their count lanes are BIT FOR BIT what wbx_fss_partial writes under the same plan and
+ * n for the float32 fields (p > a_k) and (t > a_k) with NaN kept: the same thread -> wave -> four waves order over x and field order
+ * over the depth, independent of the band size.  No atomics.  The two entries are interchangeable.
+ * Launches.  A launch carries up to 2 thresholds (the counts of a column and threshold share a 32-bit register, the circle's prefix
+ * of a threshold is one 64-bit integer in LDS); the entry cuts nthr into runs of 2 and launches them one after another on the
+ * context's stream, each writing its own lane slice of the partial (the shared count lane belongs to the first).
+ * Refused (WBX_ERR_INVALID, output untouched): everything wbx_fss_partial refuses, nthr < 1, nthr > WBX_FSS_THR_MAX, a NULL threshold
+ * table.  nkey == 0 touches nothing; ndepth == 0, nlat == 0 or nlon == 0 zero the partial. */
+#define WBX_FSS_THR_MAX 16
+int wbx_fss_threshold_partial(wbx_ctx* ctx, const wbx_fss_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int n, int nthr,
+                              const double* thresholds /* DEVICE, [nthr] */, const void* p, const void* t, const uint8_t* mask,
+                              double* partial_out);
+
 /* ---- fused binned reduction (small depth, many boolean bins) -------------------------------------------------
  * Statistic, weight and bin membership in ONE pass over p, t, c -- for chunks where little is reduced before the
  * weight/bin-dependent dims, so that the stage-1 partials would be larger than the inputs (the public benchmark's
@@ -960,7 +993,7 @@ typedef enum wbx_fn {
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
   WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28,
-  WBX_FN_ENS_BRIER_PARTIAL = 29
+  WBX_FN_ENS_BRIER_PARTIAL = 29, WBX_FN_FSS_THRESHOLD_PARTIAL = 30
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -45,6 +45,7 @@ BRIER_MAX_MEMBERS = 256  # (WBX_BRIER_MAX_MEMBERS)
 SEEPS_LANES = 1  # wbx_seeps_partial (WBX_SEEPS_LANES)
 SEEPS_CELLS = 9  # cells of its score table: 3 * (category of p) + (category of t) (WBX_SEEPS_CELLS)
 FSS_LANES = 3  # wbx_fss_partial: (Pf - Tf)^2, Pf^2, Tf^2 (WBX_FSS_LANES)
+FSS_THR_MAX = 16  # thresholds per call of wbx_fss_threshold_partial: value lane 3 k + term (WBX_FSS_THR_MAX)
 FSS_MAX_NLON = 2048  # the longitude circle's prefix lives in LDS (WBX_FSS_MAX_NLON)
 FSS_MAX_BAND_ROWS, FSS_MIN_BAND_ROWS, FSS_TARGET_BLOCKS = 64, 8, 1024  # (WBX_FSS_MAX_BAND_ROWS, ..._MIN_BAND_ROWS, ..._TARGET_BLOCKS)
 ENS_LANES = 5
@@ -70,6 +71,7 @@ EXPORTED_SYMBOLS = (
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
     'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial', 'wbx_ens_brier_partial',
+    'wbx_fss_threshold_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -80,7 +82,7 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
           'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25,
           'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28,
-          'wbx_ens_brier_partial': 29}
+          'wbx_ens_brier_partial': 29, 'wbx_fss_threshold_partial': 30}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -280,6 +282,7 @@ def load_library():
         'wbx_ens_interval_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlLaneStruct), vp, vp, vp, vp, vp],
         'wbx_seeps_partial': [vp, C.POINTER(S1PlanStruct), i32, C.c_double, vp, vp, vp, vp, i64, vp, vp],
         'wbx_fss_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, vp, vp, vp, vp],
+        'wbx_fss_threshold_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, i32, vp, vp, vp, vp, vp],
         'wbx_det_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, vp, vp, vp, vp],
         'wbx_ens_map': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp],
         'wbx_zonal_spectrum': [vp, vp, i64, i64, i64, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp],

@@ -535,7 +535,15 @@ class Aggregator:
     this package's own weightings and binnings, which look at coordinates only; a plugin from elsewhere may look at the values,
     and one that asks for the threshold coordinate does not find it -- both keep the host route."""
     lane_dims = set(stat.lane_dims)
+    thr_dim = getattr(stat, 'threshold_dim', None)  # (a thresholded lazy.LazyFSS: what its threshold dim declines is counted)
+
+    def threshold_declined(how):
+      lazy.FSS_STATS['plan_declined'] += 1
+      if len(lazy.FSS_STATS['reasons']) < 32:
+        lazy.FSS_STATS['reasons'].append(f'the threshold dim {thr_dim!r} is {how}: the host route')
     if lane_dims & reduce_set:
+      if thr_dim in reduce_set:
+        threshold_declined('reduced')
       return None
     if not stat.launchable():
       return None
@@ -555,14 +563,20 @@ class Aggregator:
       try:
         wp = self._cached_weight_product(frame)
       except KeyError:  # a coordinate the frame does not have (the threshold dim's): W is the full statistic's business
+        if thr_dim is not None:
+          threshold_declined('weighted or binned')
         return None
       if len(memo) > 16:
         memo.clear()
       memo[mkey] = (weakref.ref(frame), wp, plugins)
-    if wp is None:
+    if wp is None:  # a bin mask over a dim the frame lacks: the threshold dim's, perhaps
+      if thr_dim is not None and any(thr_dim in xr.as_dataarray(m.create_bin_mask(frame)).dims for m in self.bin_by or ()):
+        threshold_declined('weighted or binned')
       return None
     w_da, bin_dims = wp
     if lane_dims & set(bin_dims) or (w_da is not None and lane_dims & set(w_da.dims)):
+      if thr_dim in set(bin_dims) or (w_da is not None and thr_dim in set(w_da.dims)):
+        threshold_declined('weighted or binned')
       return None
     if not isinstance(stat, lazy.LazyFSS):
       return self._reduce_contingency(stat, w_da, bin_dims, use_mask, skipna)
@@ -587,7 +601,11 @@ class Aggregator:
       hit = grp.cache[key] = grp.reduce(self.reduce_dims, w_da, bin_dims, use_mask=use_mask, skipna=skipna)
     values, counts, out_dims = hit
     k, cell = int(np.prod(lane_shape, dtype=np.int64)), stat._cell  # pylint: disable=protected-access
-    values, counts = values[cell * k:(cell + 1) * k], counts[cell * k:(cell + 1) * k]
+    if getattr(stat, 'lanes_interleaved', False):  # lanes j * ncell + cell, as one call wrote them: a strided view
+      ncell = values.shape[0] // k
+      values, counts = values[cell::ncell], counts[cell::ncell]
+    else:
+      values, counts = values[cell * k:(cell + 1) * k], counts[cell * k:(cell + 1) * k]
     if len(lane_shape) != 1:  # (an axis split into the dims it stands for, or dropped where there is none: still a view)
       values, counts = values.reshape(lane_shape + values.shape[1:]), counts.reshape(lane_shape + counts.shape[1:])
     dims_in = lane_dims + tuple(out_dims)

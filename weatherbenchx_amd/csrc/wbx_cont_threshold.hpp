@@ -1,4 +1,5 @@
-// The exceedance threshold of the integer-count kernels that compare with a strict `>` (wbx_contingency.hip, wbx_ens_prob.hip, wbx_ens_brier.hip).
+// The exceedance threshold of the integer-count kernels that compare with a strict `>` (wbx_contingency.hip, wbx_ens_prob.hip, wbx_ens_brier.hip,
+// wbx_fss_thresholds.hip).
 #pragma once
 #include <cmath>
 #include <type_traits>

@@ -574,6 +574,16 @@ def seeps_available(ctx) -> bool:
     return False
 
 
+def fss_thresholds_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_fss_threshold_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_fss_threshold_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def fss_available(ctx) -> bool:
   """Whether `ctx` can launch wbx_fss_partial (see contingency_available)."""
   if not isinstance(ctx, _hip.Context):
@@ -869,7 +879,7 @@ VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
 IvlArgs = collections.namedtuple('IvlArgs', 'params')  # a HOST array of three _hip.IvlLaneStruct: no device buffer to keep
 SeepsArgs = collections.namedtuple('SeepsArgs', 'dry table cell_stride')
-FssArgs = collections.namedtuple('FssArgs', 'n')
+FssArgs = collections.namedtuple('FssArgs', 'n nthr thr')  # nthr 0, thr None: binary fields (wbx_fss_partial)
 _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
@@ -1043,11 +1053,18 @@ def _seeps_operands(ctx, devs, func, ens, cat, mdim):
 
 
 def _fss_operands(ctx, devs, func, ens, cat, mdim):
-  """`cat` = {'n': the neighbourhood size of this launch, 'wrap_longitude'}; raises what the launch would refuse."""
+  """`cat` = {'n': the neighbourhood size of this launch, 'wrap_longitude'[, 'thresholds': float64 ndarray of at most
+  _hip.FSS_THR_MAX: the inputs are continuous fields, value lane 3 k + term (wbx_fss_threshold_partial)]}; raises what the launch
+  would refuse."""
   n = int(cat['n'])
   if n < 1 or n % 2 != 1:
     raise ValueError('neighborhood_size must be odd.')
-  return _hip.FSS_LANES, None, FssArgs(n)
+  if cat.get('thresholds') is None:
+    return _hip.FSS_LANES, None, FssArgs(n, 0, None)
+  thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
+  if not 1 <= int(thr.size) <= _hip.FSS_THR_MAX:
+    raise ValueError(f'one thresholded FSS call takes 1..{_hip.FSS_THR_MAX} thresholds (got {thr.size})')
+  return _hip.FSS_LANES * int(thr.size), None, FssArgs(n, int(thr.size), _threshold_table(ctx, thr))
 
 
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
@@ -1097,8 +1114,10 @@ _KINDS = {
                    lambda d, out, dt, func, ens, cat:
                    ('wbx_seeps_partial', (dt, C.c_double(cat.dry), d[0], d[1], d[2], _table_ptr(cat.table), int(cat.cell_stride), d[3],
                                           out))),
-    'fss': _Kind(_fss_operands, (),
-                 lambda d, out, dt, func, ens, cat: ('wbx_fss_partial', (dt, int(cat.n), d[0], d[1], d[3], out))),
+    'fss': _Kind(_fss_operands, ('thr',),
+                 lambda d, out, dt, func, ens, cat:
+                 ('wbx_fss_threshold_partial', (dt, int(cat.n), int(cat.nthr), _table_ptr(cat.thr), d[0], d[1], d[3], out))
+                 if cat.thr is not None else ('wbx_fss_partial', (dt, int(cat.n), d[0], d[1], d[3], out))),
 }
 
 
@@ -1826,7 +1845,8 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   wbx_seeps_partial: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table' (float64
   [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2) / 'fss' (the three terms of the fractions
   skill score at ONE neighbourhood size, wbx_fss_partial: inputs (p, t) over one frame with `latitude` and `longitude`, `cat` = {'n',
-  'wrap_longitude'}, `mask` the mask of the statistic for that size; the plan is planner.build_fss_plan's -- x is longitude, latitude
+  'wrap_longitude'}, `mask` the mask of the statistic for that size; with 'thresholds' (float64 ndarray of at most _hip.FSS_THR_MAX) in
+  `cat` the inputs are CONTINUOUS fields and wbx_fss_threshold_partial scores (p > thr_k, t > thr_k): value lane 3 k + term; the plan is planner.build_fss_plan's -- x is longitude, latitude
   is the last key dim whatever the weights depend on, planner.FssPlanError where it cannot be --; value lanes (Pf - Tf)^2, Pf^2, Tf^2;
   the same stage 2).
 

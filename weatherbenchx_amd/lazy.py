@@ -77,6 +77,10 @@ FSS_SIZE_DIM = 'neighborhood_size'
 # reductions of fused FSS statistics that the stencil's plan could not serve and that took the host route instead, with the plan's
 # reasons (tests and tools read these, like replay.STATS)
 FSS_STATS = {'plan_declined': 0, 'reasons': []}
+# False (WBX_FUSED_FSS_THRESHOLDS=0): the FSS terms behind ContinuousToBinary('both', thresholds, dim) binarise both inputs on the host
+# route (two [frame, K] float32 indicator arrays per variable) before the statistic sees them, as before wbx_fss_threshold_partial
+# existed (A/B timing, tests).  Only effective while FUSED_FSS is on.
+FUSED_FSS_THRESHOLDS = os.environ.get('WBX_FUSED_FSS_THRESHOLDS', '1') != '0'
 # False (WBX_FUSED_BRIER=0): Error, AbsoluteError and SquaredError behind ContinuousToBinary('both') [-> EnsembleMean /
 # WeibullEnsembleToProbabilistic('predictions')] (the Brier score and its kin) build the [K, M, frame] indicator arrays on the host
 # and reduce them as before wbx_ens_brier_partial existed (A/B timing, tests).
@@ -236,7 +240,7 @@ class FusedGroup:
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
     # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
     # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
-    # per size, or None)} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic)
+    # per size, or None), 'thresholds' (float64 ndarray, or None: binary inputs), 'threshold_dim', 'coord'} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -356,17 +360,38 @@ class FusedGroup:
   def _reduce_fss(self, inputs, reduce_dims, w_da, bin_dims, use_mask, skipna):
     """The three terms of the fractions skill score: one launch per neighbourhood size (wbx_fss_partial; the shared count lane of a
     mask does not allow several sizes in one), each under the mask of the statistic for ITS size, joined on the host term by term:
-    the result is (3 * K,) + out_dims with lane term * K + k.  A scalar size is one launch and nothing is joined."""
+    the result is (3 * K,) + out_dims with lane term * K + k.  A scalar size is one launch and nothing is joined.
+    Thresholded continuous inputs (cat['thresholds']): one entry call (wbx_fss_threshold_partial) per size and block of at most
+    _hip.FSS_THR_MAX thresholds, the mask of a size serving all of them; a call's lanes 3 j + term are joined on the host into
+    (3 * K * J,) + out_dims with lane term * (K * J) + k * J + j, J the number of thresholds.  ONE call (one size, one block) is
+    handed on as it is, lanes 3 j + term (LazyFSS.lanes_interleaved tells the Aggregator): nothing is joined, so the result may
+    still be pending (deferred read-back, chunk records)."""
     cat = self.cat
     sizes, masks = list(cat['sizes']), cat['masks']
+    thr = cat.get('thresholds')
 
-    def launch(k):
+    def launch(k, thresholds=None):
+      sub = {'n': int(sizes[k]), 'wrap_longitude': bool(cat['wrap_longitude'])}
+      if thresholds is not None:
+        sub['thresholds'] = thresholds
       return engine.reduce_statistics('fss', inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims,
-                                      mask=masks[k] if (use_mask and masks is not None) else None, skipna=skipna,
-                                      cat={'n': int(sizes[k]), 'wrap_longitude': bool(cat['wrap_longitude'])})
+                                      mask=masks[k] if (use_mask and masks is not None) else None, skipna=skipna, cat=sub)
+    nl = _hip.FSS_LANES
+    if thr is not None:
+      nthr, block = int(thr.size), _hip.FSS_THR_MAX
+      cuts = [(k, j0, min(j0 + block, nthr)) for k in range(len(sizes)) for j0 in range(0, nthr, block)]
+      blocks = {j0: np.ascontiguousarray(thr[j0:j1]) for _, j0, j1 in cuts}  # (one table per block: uploaded once per contents)
+      if len(cuts) == 1:
+        return launch(0, blocks[0])
+
+      def join(parts):
+        out = np.empty((nl, len(sizes), nthr) + parts[0].shape[1:], np.float64)
+        for (k, j0, j1), a in zip(cuts, parts):  # (the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from)
+          out[:, k, j0:j1] = np.moveaxis(a.reshape((j1 - j0, nl) + a.shape[1:]), 1, 0)
+        return out.reshape((nl * len(sizes) * nthr,) + parts[0].shape[1:])
+      return _reduce_in_blocks(cuts, lambda cut: launch(cut[0], blocks[cut[1]]), join)
     if len(sizes) == 1:
       return launch(0)
-    nl = _hip.FSS_LANES
     return _reduce_in_blocks(range(len(sizes)), launch,
                              lambda parts: np.stack(parts, axis=1).reshape((nl * len(parts),) + parts[0].shape[1:]))
 
@@ -935,19 +960,28 @@ class LazyFSS(xr.LazyPickleMixin, xr.DataArray):
   """One term of the fractions skill score -- SquaredFractionsError, SquaredPredictionFraction or SquaredTargetFraction -- of (p, t)
   at a neighbourhood size, or at several along a leading `neighborhood_size` dim.  The three terms of one (p, t, sizes, wrap,
   combine_mask) share a FusedGroup of kind 'fss', so the Aggregator gets all of them from one launch per size (wbx_fss_partial).
-  Reading `.data` gives the host route's array (torch stays torch) and needs no device."""
+  Reading `.data` gives the host route's array (torch stays torch) and needs no device.
+  With thresholds in the group (fss_statistic(thresholds=...)) p and t are CONTINUOUS fields and the statistic is what the term is
+  behind ContinuousToBinary('both', thresholds, threshold_dim): the threshold dim, with its coordinate, sits where
+  binarize_thresholds followed by neighborhood_averaging puts it -- after the other non-spatial dims, before latitude and longitude --
+  and the launches are wbx_fss_threshold_partial's, one per size and block of thresholds."""
 
   def __init__(self, group: FusedGroup, term: int, host, mask=None, name=None):
     cat = group.cat
     self._data = None
     rest = tuple(d for d in group.dims if d not in ('latitude', 'longitude'))
     lead = () if cat['scalar'] else (FSS_SIZE_DIM,)
+    self._threshold_dim = cat.get('threshold_dim') if cat.get('thresholds') is not None else None
+    if self._threshold_dim is not None:
+      rest += (self._threshold_dim,)
     self._dims = lead + rest + ('latitude', 'longitude')  # the host route's order: the spatial dims end up last
     self.name = name
     self.attrs = {}
     self._coords = {k: v for k, v in group.coords.items() if k != 'mask'}
     if not cat['scalar']:
       self._coords[FSS_SIZE_DIM] = ((FSS_SIZE_DIM,), np.asarray(list(cat['sizes'])))
+    if self._threshold_dim is not None:
+      self._coords[self._threshold_dim] = ((self._threshold_dim,), np.asarray(cat['coord']))
     if mask is not None:  # what _FractionStatistic._compute_per_variable attaches
       self._coords['mask'] = (tuple(mask.dims), np.asarray(mask.values, dtype=bool))
     self._group = group
@@ -961,20 +995,36 @@ class LazyFSS(xr.LazyPickleMixin, xr.DataArray):
   # what the Aggregator's route for lane blocks asks (shared with LazyContingency)
   @property
   def lane_dims(self) -> tuple:
-    return () if self._group.cat['scalar'] else (FSS_SIZE_DIM,)
+    lead = () if self._group.cat['scalar'] else (FSS_SIZE_DIM,)
+    return lead + ((self._threshold_dim,) if self._threshold_dim is not None else ())
 
   @property
   def lane_shape(self) -> tuple:
-    return () if self._group.cat['scalar'] else (len(self._group.cat['sizes']),)
+    lead = () if self._group.cat['scalar'] else (len(self._group.cat['sizes']),)
+    return lead + ((int(self._group.cat['thresholds'].size),) if self._threshold_dim is not None else ())
+
+  @property
+  def threshold_dim(self):
+    """The threshold dim of a thresholded statistic, else None."""
+    return self._threshold_dim
+
+  @property
+  def lanes_interleaved(self) -> bool:
+    """Whether the group's reduction comes as lanes 3 j + term (one call of wbx_fss_threshold_partial, handed on unjoined) instead
+    of term * K + k (FusedGroup._reduce_fss)."""
+    cat = self._group.cat
+    return self._threshold_dim is not None and len(cat['sizes']) == 1 and int(cat['thresholds'].size) <= _hip.FSS_THR_MAX
 
   @property
   def result_dims(self) -> tuple:
     return self._dims
 
-  @staticmethod
-  def launchable() -> bool:
+  def launchable(self) -> bool:
     try:
-      return FUSED_FSS and engine.fss_available(_hip.default_context())
+      ctx = _hip.default_context()
+      if self._threshold_dim is not None:
+        return FUSED_FSS and FUSED_FSS_THRESHOLDS and engine.fss_available(ctx) and engine.fss_thresholds_available(ctx)
+      return FUSED_FSS and engine.fss_available(ctx)
     except _hip.WbxUnavailableError:
       return False
 
@@ -989,26 +1039,39 @@ class LazyFSS(xr.LazyPickleMixin, xr.DataArray):
   @property
   def shape(self):
     sizes = dict(self._group.sizes, **{FSS_SIZE_DIM: len(self._group.cat['sizes'])})
+    if self._threshold_dim is not None:
+      sizes[self._threshold_dim] = int(self._group.cat['thresholds'].size)
     return tuple(sizes[d] for d in self._dims)
 
   @property
   def dtype(self):
-    wide = str(self._group.p.dtype) == 'float64' and 1 in [int(n) for n in self._group.cat['sizes']]
+    wide = (self._threshold_dim is None and str(self._group.p.dtype) == 'float64'
+            and 1 in [int(n) for n in self._group.cat['sizes']])  # (binarised fields are float32 whatever the inputs are)
     return np.dtype(np.float64 if wide else np.float32)
 
 
-def fss_statistic(term: int, p, t, sizes, wrap_longitude: bool, mask, *, combine_mask: bool = False, host=None, name=None) -> xr.DataArray:
+def fss_statistic(term: int, p, t, sizes, wrap_longitude: bool, mask, *, combine_mask: bool = False, host=None, name=None,
+                  thresholds=None, threshold_dim=None) -> xr.DataArray:
   """Term `term` (FSS_TERM) of the fractions skill score of (p, t) as a LazyFSS.  `sizes`: one odd neighbourhood size or a sequence
   of them (a leading `neighborhood_size` dim); `mask`: what spatial.get_fss_mask returns for these sizes (a Boolean DataArray, the
   size dim leading where there are several) or None -- the mask of the STATISTIC, the kernel does not erode masks; `host()`: the host
-  route's DataArray, which whoever reads the per-point values gets.  One group per (p, t, sizes, wrap, combine_mask): the three terms
-  of one FSS meet in it."""
+  route's DataArray, which whoever reads the per-point values gets.  `thresholds` (the plain sequence of real numbers a
+  ContinuousToBinary was built with) and `threshold_dim`: p and t are continuous fields and the term is that of (p > thr, t > thr)
+  along `threshold_dim`; the mask has no threshold dim and serves every threshold.  One group per (p, t, sizes, wrap, combine_mask,
+  thresholds): the three terms of one FSS meet in it."""
   p, t = xr.as_dataarray(p), xr.as_dataarray(t)
   scalar = not isinstance(sizes, (list, tuple, np.ndarray))
   size_list = [int(sizes)] if scalar else [int(n) for n in sizes]
-  ckey = ('fss', tuple(size_list), scalar, bool(wrap_longitude), bool(combine_mask))
+  thr = coord = None
+  if thresholds is not None:
+    if threshold_dim is None or threshold_dim in p.dims or threshold_dim in t.dims:
+      raise ValueError(f'{threshold_dim!r} must be a new dimension of the inputs')
+    coord = np.asarray(list(thresholds))
+    thr = np.asarray(list(thresholds), np.float64).reshape(-1)
+  ckey = ('fss', tuple(size_list), scalar, bool(wrap_longitude), bool(combine_mask), threshold_dim if thr is not None else None,
+          thr.tobytes() if thr is not None else None)
   grp = _group_for('fss', p, t, clim_key=ckey, cat={'sizes': size_list, 'scalar': scalar, 'wrap_longitude': bool(wrap_longitude),
-                                                     'masks': None})
+                                                     'masks': None, 'thresholds': thr, 'threshold_dim': threshold_dim, 'coord': coord})
   if mask is not None and grp.cat['masks'] is None:  # one DataArray per size: its device copy is cached on the object
     vals = np.asarray(mask.values, dtype=bool)
     mdims = tuple(mask.dims)

@@ -1,7 +1,9 @@
 """Fractions skill score and its neighbourhood averaging (counterpart of weatherbenchX/metrics/spatial.py:24-339).
 
 Outside the path SURVEY section 8 names.  Under the Aggregator the three per-point statistics of a (predictions, targets) pair are the
-value lanes of one fused launch per neighbourhood size (wbx_fss_partial, `_FractionStatistic._fused`).  The host route, which
+value lanes of one fused launch per neighbourhood size (wbx_fss_partial, `_FractionStatistic._fused`); behind
+`wrappers.ContinuousToBinary('both', thresholds, dim)` the launch takes the continuous fields and the thresholds
+(wbx_fss_threshold_partial, `_FractionStatistic.compute_with_transform`).  The host route, which
 everything the gate declines takes and which whoever reads `.values` gets: the neighbourhood means are sliding-window sums on
 whatever holds the payload (NumPy on the host, torch for a chunk in HBM), the three per-point statistics are squares of them, and
 their weighted, binned, masked means are the Aggregator's reduction like every other statistic.
@@ -22,6 +24,7 @@ from weatherbenchx_amd import engine
 from weatherbenchx_amd import lazy
 from weatherbenchx_amd import xarray_lite as xr
 from weatherbenchx_amd.metrics import base
+from weatherbenchx_amd.metrics import wrappers
 
 _SPATIAL = ('latitude', 'longitude')
 
@@ -181,44 +184,92 @@ class _FractionStatistic(base.PerVariableStatistic):
     dim (planner.build_fss_plan); `longitude` is x and can always be kept.  The result has the host route's dims, name and
     coordinates, its `mask` coordinate among them (computed on the host as before: the kernel does not erode masks), and its
     `.values` are the host route's."""
-    term = lazy.FSS_TERM.get(type(self).__name__)
-    if not lazy.FUSED_FSS or term is None:
-      return None
     p, t = predictions, targets
+    if not self._launchable_on(p, t):
+      return None
+    sizes = self.neighborhood_size_in_pixels
+    mask = self._mask_in_host_order(p, t)
+    return lazy.fss_statistic(lazy.FSS_TERM[type(self).__name__], p, t, sizes if isinstance(sizes, Iterable) else int(sizes),
+                              self.wrap_longitude, mask, combine_mask=self.combine_mask,
+                              host=lambda: self.host_per_variable(p, t), name=p.name)
+
+  def _mask_in_host_order(self, p, t):
+    """get_fss_mask of the inputs with its dims in the host route's order (the size dim leading), or None."""
+    sizes = self.neighborhood_size_in_pixels
+    mask = get_fss_mask(p, t, sizes, self.wrap_longitude, self.combine_mask)
+    if mask is None:
+      return None
+    lead = (lazy.FSS_SIZE_DIM,) if isinstance(sizes, Iterable) else ()
+    order = lead + tuple(d for d in p.dims if d not in _SPATIAL) + _SPATIAL  # the host route's dims
+    return mask.transpose(*[d for d in order if d in mask.dims])
+
+  def _launchable_on(self, p, t, thresholded: bool = False) -> bool:
+    """The gate `_fused` documents, on the fields a launch would read: the binary inputs, or (`thresholded`) the continuous inputs
+    in front of a ContinuousToBinary, for which the switch WBX_FUSED_FSS_THRESHOLDS and the entry wbx_fss_threshold_partial are
+    asked for as well.  Never raises."""
+    term = lazy.FSS_TERM.get(type(self).__name__)
+    if not lazy.FUSED_FSS or term is None or (thresholded and not lazy.FUSED_FSS_THRESHOLDS):
+      return False
     dtype = str(p.dtype)
     if dtype not in ('float32', 'float64') or str(t.dtype) != dtype:
-      return None
+      return False
     if set(p.dims) != set(t.dims) or not set(_SPATIAL) <= set(p.dims) or any(p.sizes[d] != t.sizes[d] for d in p.dims):
-      return None
+      return False
     for d in p.dims:
       if (d in p.coords) != (d in t.coords) or (d in p.coords and not xr._values_equal(p.coords[d].values, t.coords[d].values)):  # pylint: disable=protected-access
-        return None
+        return False
     sizes = self.neighborhood_size_in_pixels
     size_list = [sizes] if not isinstance(sizes, Iterable) else list(sizes)
     if isinstance(sizes, Iterable) and not isinstance(sizes, (list, tuple, np.ndarray)):
-      return None
+      return False
     nlat, nlon = int(p.sizes['latitude']), int(p.sizes['longitude'])
     if not size_list or nlon > _hip.FSS_MAX_NLON:
-      return None
+      return False
     for n in size_list:
       if int(n) != n or n < 1 or n % 2 != 1 or (n > 1 and n > min(nlat, nlon)):
-        return None
+        return False
     if lazy.payload_layout(p).stride('longitude') != 1 or lazy.payload_layout(t).stride('longitude') != 1:
-      return None
+      return False
     try:
       ctx = _hip.default_context()
     except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+      return False
+    return engine.fss_available(ctx) and (not thresholded or engine.fss_thresholds_available(ctx))
+
+  def compute_with_transform(self, transform, predictions, targets):
+    """This term behind `wrappers.ContinuousToBinary('both', [numbers], dim)` as lazy statistics on the CONTINUOUS inputs (one call
+    of wbx_fss_threshold_partial per size and block of thresholds for the three terms of a variable, lazy.fss_statistic with
+    thresholds), or None: the caller then transforms and computes as usual, which is the route before the entry existed.  None for
+    any other transform or `which`, thresholds that are not a plain sequence of real numbers (labelled ones), a threshold dim that
+    is already on either input, whatever `_fused` declines on the continuous inputs, WBX_FUSED_FSS_THRESHOLDS=0 (or
+    WBX_FUSED_FSS=0), no device, or no such entry in the library.  The mask of a size is get_fss_mask of the inputs: the `mask`
+    coordinate has no threshold dim and serves every threshold.  The result has the host route's dims (the threshold dim after the
+    other non-spatial dims and before latitude and longitude, behind a leading `neighborhood_size`), name and coordinates, and its
+    `.values` are the host route's.  The gate never raises: where the host route would, it does."""
+    if not lazy.FUSED_FSS or not lazy.FUSED_FSS_THRESHOLDS or type(self).__name__ not in lazy.FSS_TERM:
       return None
-    if not engine.fss_available(ctx):
+    if type(transform) is not wrappers.ContinuousToBinary or transform.which != 'both':  # pylint: disable=unidiomatic-typecheck
       return None
-    mask = get_fss_mask(p, t, sizes, self.wrap_longitude, self.combine_mask)
-    lead = (lazy.FSS_SIZE_DIM,) if isinstance(sizes, Iterable) else ()
-    order = lead + tuple(d for d in p.dims if d not in _SPATIAL) + _SPATIAL  # the host route's dims
-    if mask is not None:
-      mask = mask.transpose(*[d for d in order if d in mask.dims])
-    return lazy.fss_statistic(term, p, t, sizes if isinstance(sizes, Iterable) else int(sizes),
-                              self.wrap_longitude, mask, combine_mask=self.combine_mask,
-                              host=lambda: self.host_per_variable(p, t), name=p.name)
+    values = wrappers.plain_thresholds(transform._threshold_value)  # pylint: disable=protected-access
+    dim = transform._threshold_dim  # pylint: disable=protected-access
+    if values is None:
+      return None
+    pairs = {}
+    for name in predictions.keys():
+      if name not in targets.keys():
+        continue
+      p, t = base._named(predictions[name], name), base._named(targets[name], name)  # pylint: disable=protected-access
+      if dim in p.dims or dim in t.dims or not self._launchable_on(p, t, thresholded=True):
+        return None
+      pairs[name] = (p, t)
+    sizes = self.neighborhood_size_in_pixels
+    sizes = sizes if isinstance(sizes, Iterable) else int(sizes)
+
+    def one(p, t):
+      host = lambda: self.host_per_variable(wrappers.binarize_thresholds(p, values, dim), wrappers.binarize_thresholds(t, values, dim))
+      return lazy.fss_statistic(lazy.FSS_TERM[type(self).__name__], p, t, sizes, self.wrap_longitude, self._mask_in_host_order(p, t),
+                                combine_mask=self.combine_mask, host=host, name=p.name, thresholds=values, threshold_dim=dim)
+    return {name: one(p, t) for name, (p, t) in pairs.items()}
 
 
 @dataclasses.dataclass
