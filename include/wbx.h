@@ -416,6 +416,30 @@ int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_
                         int nthr, const double* p_thresholds, const double* t_thresholds /* DEVICE float64[nthr] each */,
                         int right_inclusive, const void* p, const void* t, const uint8_t* mask, double* partial_out);
 
+/* ---- stage 1: ranked probability score of an ensemble at threshold FIELDS (joined ABI 13) -----------------------
+ * wbx_ens_rps_partial with the thresholds read at the point: EnsembleRankedProbabilityScore with `prediction_bin_thresholds` /
+ * `target_bin_thresholds` Datasets such as climatological terciles [bin, dayofyear, latitude, longitude], without the selected copy of
+ * the thresholds (select_bin_thresholds_by_time_from_chunk) and the indicator arrays.  `c` is input 2 of the plan (key_off[2],
+ * depth_off[2], xstride[2], the gather tables; zero strides where it does not vary), exactly as for wbx_ens_interval_partial.  With A
+ * the address of a point in c, in elements of `thr_dtype`:
+ *     a_k = c[A + k * thr_stride],   b_k = c[A + k * thr_stride + t_off],   k in 0..nthr-1
+ * t_off == 0: both sides read the same thresholds, which are loaded once.  c_k, o_k, n_k, D, the value, the partial (S / D of two
+ * integers, no atomics), the lanes and the layout of partial_out are those of wbx_ens_rps_partial.
+ * A point is a NaN point if a member, the target, or any of its nthr prediction or target thresholds is NaN
+ * (cdf.where(~isnan(da)).where(~isnan(thresholds)) followed by sum(bin_dim, skipna=False)); NaN points poison, are masked out or are
+ * counted out as for wbx_ens_rps_partial.  Only the nthr thresholds of a side are read.
+ * Comparisons decide as NumPy's promoted comparison does: equal types compare as they are; float32 thresholds against float64 data
+ * widen exactly; float64 thresholds against float32 data are rounded per point to float32 toward -inf for `<=` and toward +inf for
+ * `<` (NaN stays NaN, a value beyond the float32 range decides right) and compared in float32.
+ * Refused (WBX_ERR_INVALID, output untouched): everything wbx_ens_rps_partial refuses (limits WBX_ERPS_MAX_*), an unknown thr_dtype,
+ * thr_stride == 0 with nthr > 1, and a NULL c unless the extent is empty (as for p and t: nothing would be read).  vec = 4 is
+ * accepted and read with dword loads; no plane mode, no x weights.
+ * nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial, whatever c is. */
+int wbx_ens_rps_field_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* p, t: WBX_F32 | WBX_F64 */,
+                              int thr_dtype /* c: WBX_F32 | WBX_F64 */, int M, int64_t member_stride, int nthr, int64_t thr_stride,
+                              int64_t t_off, int right_inclusive, const void* p, const void* t, const void* c, const uint8_t* mask,
+                              double* partial_out);
+
 /* ---- stage 1: energy score of an ensemble, both terms (joined ABI 13) -------------------------------------------
  * EnergyScoreSkill and EnergyScoreSpread (probabilistic.py:480-551) of an ensemble of predictions against a target, in one pass
  * over p and t instead of one whole-array pass per cyclic member offset.  p has a member axis of length M and element stride
@@ -993,7 +1017,7 @@ typedef enum wbx_fn {
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
   WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28,
-  WBX_FN_ENS_BRIER_PARTIAL = 29, WBX_FN_FSS_THRESHOLD_PARTIAL = 30
+  WBX_FN_ENS_BRIER_PARTIAL = 29, WBX_FN_FSS_THRESHOLD_PARTIAL = 30, WBX_FN_ENS_RPS_FIELD_PARTIAL = 31
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

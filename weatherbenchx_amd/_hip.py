@@ -22,7 +22,7 @@ DET_INPUTS = {DET3: 2, DET6: 3, PASS1: 1}
 CAT_EXCEED, CAT_RANK = 0, 1
 CONT_CELLS = 4  # wbx_contingency_partial: value lane cell * nthr + k, cell in (TP, FP, FN, TN)
 CONT_MAX_THRESHOLDS = 16  # per launch (WBX_CONT_MAX_THRESHOLDS)
-ERPS_MAX_THRESHOLDS = 16  # wbx_ens_rps_partial, per launch (WBX_ERPS_MAX_THRESHOLDS)
+ERPS_MAX_THRESHOLDS = 16  # wbx_ens_rps_partial and wbx_ens_rps_field_partial, per launch (WBX_ERPS_MAX_THRESHOLDS)
 ERPS_MAX_MEMBERS = 256  # (WBX_ERPS_MAX_MEMBERS: a point's integer numerator fits an int32)
 ENRG_LANES = 2  # wbx_ens_energy_partial: skill, spread (WBX_ENRG_LANES)
 ENRG_MAX_MEMBERS = 64  # (WBX_ENRG_MAX_MEMBERS)
@@ -71,7 +71,7 @@ EXPORTED_SYMBOLS = (
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
     'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial', 'wbx_ens_brier_partial',
-    'wbx_fss_threshold_partial',
+    'wbx_fss_threshold_partial', 'wbx_ens_rps_field_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -82,7 +82,8 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_contingency_partial': 20, 'wbx_ens_rps_partial': 21, 'wbx_ens_energy_partial': 22,
           'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25,
           'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28,
-          'wbx_ens_brier_partial': 29, 'wbx_fss_threshold_partial': 30}
+          'wbx_ens_brier_partial': 29, 'wbx_fss_threshold_partial': 30,
+          'wbx_ens_rps_field_partial': 31}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -274,6 +275,7 @@ def load_library():
         'wbx_cat_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i32, i64, vp, vp, vp, vp, vp],
         'wbx_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, vp, vp, vp, vp, vp],
         'wbx_ens_rps_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp],
+        'wbx_ens_rps_field_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i64, i32, i64, i64, i32, vp, vp, vp, vp, vp],
         'wbx_ens_energy_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, vp, vp, vp, vp],
         'wbx_ens_variogram_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, i32, vp, vp, vp, vp],
         'wbx_ens_wasserstein_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i64, vp, vp, vp, vp],

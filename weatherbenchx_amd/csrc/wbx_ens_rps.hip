@@ -15,102 +15,19 @@
 // plan), a function of the inputs and the plan only.
 // x summed: a lane owns a point of the row, the end is an integer wave reduction and an integer sum over the block's waves
 // through LDS.  x kept: a lane owns an x and walks the chunk's rows; no cross-lane traffic.
-#include <cmath>
-#include <type_traits>
-
-#include "wbx_s1.hpp"
+#include "wbx_ens_rps.hpp"
 
 namespace wbx {
 
-constexpr int ERPS_MAX_WAVES = 4;
-constexpr int ERPS_FLIGHT = 8;  // member loads in flight per lane
-
-// Threshold k as the type the compare runs in, wave-uniform (SGPRs).  float: for every float32 x
-//   x <= thr (in float64) <=> x <= rd(thr) (in float32), rd = rounding toward -inf   (cont_threshold of wbx_contingency.hip)
-//   x <  thr (in float64) <=> x <  ru(thr) (in float32), ru = rounding toward +inf
-// and rounding to nearest is equivalent to neither (float(0.1) <= 0.1 is false).  Beyond the float32 range rd gives FLT_MAX /
-// -inf and ru +inf / -FLT_MAX, which decide right as well.
+// Threshold k as the type the compare runs in, wave-uniform (SGPRs).  float: rounded as erps_round says.
 template <typename T, bool RIGHT>
 __device__ __forceinline__ T erps_threshold(const double* thr, int k) {
   const double v = ((const_ptr<double>)thr)[k];
   if constexpr (std::is_same<T, double>::value) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
   } else {
-    float f = (float)v;  // to nearest
-    const uint32_t b = __float_as_uint(f);
-    if constexpr (RIGHT) {
-      if ((double)f > v) f = __uint_as_float(f > 0.f ? b - 1u : (f < 0.f ? b + 1u : 0x80000001u));  // one step down
-    } else {
-      if ((double)f < v) f = __uint_as_float(f > 0.f ? b + 1u : (f < 0.f ? b - 1u : 0x00000001u));  // one step up
-    }
-    return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(f)));
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(erps_round<RIGHT>(v))));
   }
-}
-
-template <bool RIGHT, typename T>
-__device__ __forceinline__ bool erps_below(T x, T thr) {
-  if constexpr (RIGHT)
-    return x <= thr;
-  else
-    return x < thr;
-}
-
-// The integer numerator sum_k n_k of the point whose members start at `pm` (element stride `ms`) and whose target is `y`;
-// `nan` says whether a member or the target is NaN (the numerator is then meaningless).  Slots k >= nthr are skipped.
-template <typename T, int NT, bool RIGHT>
-__device__ __forceinline__ int32_t erps_point(const T* pm, int64_t ms, int M, T y, const T (&pa)[NT], const T (&tb)[NT], int nthr,
-                                              bool fair, bool& nan) {
-  int32_t c[NT];
-#pragma unroll
-  for (int q = 0; q < NT; ++q) c[q] = 0;
-  bool bad = y != y;
-  int m = 0;
-  for (; m + ERPS_FLIGHT <= M; m += ERPS_FLIGHT) {
-    T v[ERPS_FLIGHT];
-#pragma unroll
-    for (int u = 0; u < ERPS_FLIGHT; ++u) v[u] = ld_stream(pm + (int64_t)(m + u) * ms);
-#pragma unroll
-    for (int u = 0; u < ERPS_FLIGHT; ++u) {
-      bad |= v[u] != v[u];
-#pragma unroll
-      for (int q = 0; q < NT; ++q) c[q] += erps_below<RIGHT>(v[u], pa[q]) ? 1 : 0;
-    }
-  }
-  if (m < M) {  // the last, short group: the loads past the end re-read the last member and are not counted
-    T v[ERPS_FLIGHT];
-#pragma unroll
-    for (int u = 0; u < ERPS_FLIGHT; ++u) v[u] = ld_stream(pm + (int64_t)(m + u < M ? m + u : M - 1) * ms);
-#pragma unroll
-    for (int u = 0; u < ERPS_FLIGHT; ++u) {
-      if (m + u < M) {
-        bad |= v[u] != v[u];
-#pragma unroll
-        for (int q = 0; q < NT; ++q) c[q] += erps_below<RIGHT>(v[u], pa[q]) ? 1 : 0;
-      }
-    }
-  }
-  nan = bad;
-  int32_t n = 0;
-#pragma unroll
-  for (int q = 0; q < NT; ++q) {
-    if (q < nthr) {
-      const int32_t e = c[q] - (erps_below<RIGHT>(y, tb[q]) ? M : 0);
-      n += fair ? (M - 1) * e * e - c[q] * (M - c[q]) : e * e;
-    }
-  }
-  return n;
-}
-
-// One partial from its integer sums: S = sum of the numerators over the good (valid, non-NaN) points.
-__device__ __forceinline__ void erps_write(double* o, int64_t nj, uint32_t flags, double denom, int64_t s, int64_t ngood,
-                                           int64_t nvalid) {
-  const bool skipna = flags & WBX_FLAG_SKIPNA;
-  const bool poisoned = !skipna && ngood != nvalid;  // a NaN under a valid point
-  o[0] = poisoned ? (double)NAN : (double)s / denom;
-  if (skipna)
-    o[nj] = (double)ngood;
-  else if (flags & WBX_FLAG_MASKED)
-    o[nj] = (double)nvalid;
 }
 
 // x summed.  grid = nkey * nchunk, block = plan->block_threads; rows are dealt to the waves as in s1_xr_kernel.
@@ -238,24 +155,9 @@ extern "C" int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dt
                                    const double* p_thresholds, const double* t_thresholds, int right_inclusive, const void* p,
                                    const void* t, const uint8_t* mask, double* partial_out) {
   using namespace wbx;
-  // int32 numerator of a point: K (M - 1) M^2 < 2^31
-  static_assert((int64_t)WBX_ERPS_MAX_THRESHOLDS * (WBX_ERPS_MAX_MEMBERS - 1) * WBX_ERPS_MAX_MEMBERS * WBX_ERPS_MAX_MEMBERS < ((int64_t)1 << 31),
-                "a point's numerator must fit an int32");
   const S1Names names = {"wbx_ens_rps_partial: ", "partial_out", "p/t"};
   if (int rc = s1_begin(names.who, ctx, plan)) return rc;
-  WBX_REQUIRE(nthr >= 1 && nthr <= WBX_ERPS_MAX_THRESHOLDS, "wbx_ens_rps_partial: 1..%d thresholds per launch (got %d)",
-              WBX_ERPS_MAX_THRESHOLDS, nthr);
-  WBX_REQUIRE(M >= 1 && M <= WBX_ERPS_MAX_MEMBERS, "wbx_ens_rps_partial: 1..%d members (got %d)", WBX_ERPS_MAX_MEMBERS, M);
-  WBX_REQUIRE(dtype == WBX_F32 || dtype == WBX_F64, "wbx_ens_rps_partial: unknown dtype %d", dtype);
-  WBX_REQUIRE(!(plan->flags & ~(WBX_FLAG_MASKED | WBX_FLAG_SKIPNA | WBX_FLAG_FAIR)),
-              "wbx_ens_rps_partial: flags other than MASKED | SKIPNA | FAIR (0x%x)", plan->flags);
-  const bool fair = plan->flags & WBX_FLAG_FAIR;
-  WBX_REQUIRE(!fair || M >= 2, "wbx_ens_rps_partial: the fair score needs at least 2 members (got %d)", M);
-  WBX_REQUIRE(plan->plane_rows == 0 && plan->x_weights == nullptr, "wbx_ens_rps_partial: no plane mode, no folded x weights");
-  // |S| stays exact in fp64: a partial meets at most depth_chunk * nx points of at most nthr (M - 1) M^2 each
-  WBX_REQUIRE((double)plan->depth_chunk * (double)(plan->nx > 0 ? plan->nx : 1) * (double)nthr * (double)(M > 1 ? M - 1 : 1) * (double)M *
-                      (double)M < 9007199254740992.0,
-              "wbx_ens_rps_partial: 2^53 or more per partial (depth_chunk * nx * nthr * (M - 1) * M^2)");
+  if (int rc = erps_requirements(names.who, plan, dtype, M, nthr)) return rc;
   S1Args a;
   if (int rc = s1_operands(names, ctx, plan, 2, p, t, mask, partial_out, a)) return rc;
   const int nacc = (int)partial_lanes(plan->flags, 1);
@@ -264,7 +166,7 @@ extern "C" int wbx_ens_rps_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dt
   WBX_REQUIRE(p_thresholds != nullptr && t_thresholds != nullptr, "wbx_ens_rps_partial: a threshold table is NULL");
   a.M = M;
   a.mstride = member_stride;
-  const double denom = fair ? (double)M * (double)M * (double)(M - 1) : (double)M * (double)M;
+  const double denom = erps_denominator(plan->flags & WBX_FLAG_FAIR, M);
   if (dtype == WBX_F32)
     return right_inclusive ? erps_dispatch<float, true>(ctx, plan, a, p_thresholds, t_thresholds, nthr, nacc, denom)
                            : erps_dispatch<float, false>(ctx, plan, a, p_thresholds, t_thresholds, nthr, nacc, denom);

@@ -82,6 +82,11 @@ def _common_dtype(datas) -> int:
   return _hip.F64 if f64 else _hip.F32
 
 
+def own_dtype(da: xr.DataArray) -> int:
+  """The dtype code of a float32 / float64 payload as it is."""
+  return _common_dtype([da.data])
+
+
 def _to_device(ctx: _hip.Context, da: xr.DataArray, dtype_code: int) -> _Dev:
   """Device view of a DataArray's payload in dtype `dtype_code` (cached per object and dtype)."""
   cache = da.__dict__.setdefault('_wbx_dev', {})
@@ -504,6 +509,16 @@ def ens_rps_available(ctx) -> bool:
     return False
 
 
+def ens_rps_field_available(ctx) -> bool:
+  """Whether `ctx` can launch wbx_ens_rps_field_partial (see contingency_available)."""
+  if not isinstance(ctx, _hip.Context):
+    return False
+  try:
+    return getattr(ctx.lib, 'wbx_ens_rps_field_partial', None) is not None
+  except AttributeError:
+    return False
+
+
 def ens_energy_available(ctx) -> bool:
   """Whether `ctx` can launch wbx_ens_energy_partial (see contingency_available)."""
   if not isinstance(ctx, _hip.Context):
@@ -872,6 +887,7 @@ Ens2Args = collections.namedtuple('Ens2Args', 'm mstride n_t tstride')
 CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  # thr: a table; None with cstride: a field (input 2)
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
+RpsFieldArgs = collections.namedtuple('RpsFieldArgs', 'thr_dtype nthr thr_stride t_off right')  # (the field itself is input 2)
 EpcArgs = collections.namedtuple('EpcArgs', 'nthr thr nslot slots')
 BrierEnsArgs = collections.namedtuple('BrierEnsArgs', 'm mstride denom')
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
@@ -907,6 +923,23 @@ def _erps_operands(ctx, devs, func, ens, cat, mdim):
     raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
   return 1, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), RpsArgs(
       nthr, _threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
+
+
+def _erpsf_operands(ctx, devs, func, ens, cat, mdim):
+  """`cat` = {'bin_dim', 'nthr', 'side_dim' (the dim two stacked fields lie along, prediction first, or None: one field for both
+  sides), 'right_inclusive'}; the threshold field is input 2, in its own dtype."""
+  if devs[2] is None:
+    raise ValueError('the ensemble RPS at threshold fields needs the field (input 2)')
+  nthr = int(cat['nthr'])
+  if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS:
+    raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} thresholds (got {nthr})')
+  if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
+    raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
+  lay = devs[2].layout
+  thr_stride = lay.stride(cat['bin_dim']) if nthr > 1 else (lay.stride(cat['bin_dim']) or 1)
+  t_off = lay.stride(cat['side_dim']) if cat.get('side_dim') else 0
+  return 1, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), RpsFieldArgs(devs[2].dtype_code, nthr, thr_stride, t_off,
+                                                                              bool(cat['right_inclusive']))
 
 
 def _epc_operands(ctx, devs, func, ens, cat, mdim):
@@ -1094,6 +1127,10 @@ _KINDS = {
                   lambda d, out, dt, func, ens, cat:
                   ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
                                            int(bool(cat.right)), d[0], d[1], d[3], out))),
+    'erpsf': _Kind(_erpsf_operands, (),  # (the threshold field is input 2: kept like a climatology behind a gather table)
+                   lambda d, out, dt, func, ens, cat:
+                   ('wbx_ens_rps_field_partial', (dt, int(cat.thr_dtype), *map(int, ens), int(cat.nthr), int(cat.thr_stride),
+                                                  int(cat.t_off), int(bool(cat.right)), d[0], d[1], d[2], d[3], out))),
     'epc': _Kind(_epc_operands, ('thr', 'slots'),
                  lambda d, out, dt, func, ens, cat:
                  ('wbx_ens_prob_contingency_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), int(cat.nslot),
@@ -1823,7 +1860,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   wbx_contingency_partial: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
   cell * nthr + k, cell in (TP, FP, FN, TN)) / 'erps' (ranked probability score of an ensemble, wbx_ens_rps_partial: `cat` =
   {'p_thresholds', 't_thresholds' (float64 ndarrays of equal size, at most _hip.ERPS_MAX_THRESHOLDS), 'right_inclusive'},
-  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits) / 'enrg' (energy
+  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits) / 'erpsf' (the same
+  score at threshold fields, wbx_ens_rps_field_partial: inputs (p, t, threshold field behind `gather`, in its own dtype), `cat` =
+  {'bin_dim', 'nthr', 'side_dim' (of two stacked fields, or None), 'right_inclusive'}, `ens` as for 'erps'; the same stage 2) / 'enrg' (energy
   score of an ensemble, wbx_ens_energy_partial: `ens` = {'member_dim', 'M', 'fair', 'norm_dims', 'norm_sizes'}, `dims` without the
   member dim and the norm dims, which must be one strided run of both inputs; value lanes skill, spread; always stage 1, then
   wbx_contract / wbx_contract_bits: no folded x weights, no binned route) / 'vgrm' (variogram score of an ensemble,
@@ -1867,9 +1906,11 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   wdep = set(w_da.dims) - set(bin_dims) if w_da is not None else set()
   member_dim = ens['member_dim'] if ens else (cat.get('member_dim') if cat else None)
   datas = [i.data if i is not None else None for i in inputs]
-  dtype_code = _common_dtype(datas)
+  # (kind 'erpsf': the threshold field, input 2, stays in its own type -- the kernel compares as NumPy promotes)
+  dtype_code = _common_dtype(datas[:2] if kind == 'erpsf' else datas)
   _sync_torch_producers(datas)
-  devs = [(_to_device(ctx, i, dtype_code) if i is not None else None) for i in inputs]
+  devs = [(_to_device(ctx, i, own_dtype(i) if (kind == 'erpsf' and k == 2) else dtype_code) if i is not None else None)
+          for k, i in enumerate(inputs)]
   while len(devs) < 4:
     devs.append(None)
   thr_field = cat.get('thr_field') if cat else None
@@ -1924,7 +1965,7 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
   replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in _KINDS[kind].keep),
-              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None)) else None,
+              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None or kind == 'erpsf')) else None,
               # (a mask that outlives the chunk: the places whose dry fraction is in range, kind 'seeps')
               devs[3] if (mask is not None and cat and cat.get('mask_da') is mask) else None)
   bin_shape = w_buf.bin_shape

@@ -8,7 +8,8 @@ names on, so `probabilistic.EnergyScore` etc. resolve as in the reference.
 
 Four exceptions, all in how the Aggregator gets its sums -- the per-point values anybody reads are still this arithmetic:
 EnsembleRankedProbabilityScore at one plain list of thresholds is reduced by a kernel of its own, wbx_ens_rps_partial
-(lazy.ens_rps_statistic); EnergyScoreSkill and EnergyScoreSpread of one (predictions, targets) pair -- EnergyScore,
+(lazy.ens_rps_statistic), and at threshold fields (a DataArray / Dataset such as climatological terciles) by
+wbx_ens_rps_field_partial (rps_field_route, lazy.ens_rps_field_statistic); EnergyScoreSkill and EnergyScoreSpread of one (predictions, targets) pair -- EnergyScore,
 TiledEnergyScore -- by one launch of wbx_ens_energy_partial (lazy.energy_statistic); VariogramScore -- TiledVariogramScore -- at
 p = 0.5, 1 or 2 by one launch of wbx_ens_variogram_partial (lazy.variogram_statistic); WassersteinDistance between ensembles of at
 most 64 members a side by one launch of wbx_ens_wasserstein_partial (lazy.wasserstein_statistic).
@@ -88,7 +89,10 @@ class EnsembleRankedProbabilityScore(base.PerVariableStatistic):
   def _fused_per_variable(self, predictions, targets):
     """The score as a lazy statistic that the Aggregator reduces with one launch of wbx_ens_rps_partial (lazy.ens_rps_statistic),
     or None when the combination is not the plain one: numbers for thresholds, an ensemble of predictions against scalar-valued
-    targets, no per-point member counts.  Reading the statistic's values still computes them on the host."""
+    targets, no per-point member counts.  Thresholds that are fields (DataArray / Dataset) go to _fused_field_per_variable.
+    Reading the statistic's values still computes them on the host."""
+    if any(isinstance(v, (xr.DataArray, xr.Dataset)) for v in self._thresholds):
+      return self._fused_field_per_variable(predictions, targets)
     if not lazy.FUSED_ENS_RPS or self._skipna_ensemble:
       return None
     pa, tb = (wrappers.plain_thresholds(v) for v in self._thresholds)
@@ -117,6 +121,132 @@ class EnsembleRankedProbabilityScore(base.PerVariableStatistic):
     if not engine.ens_rps_available(ctx):
       return None
     return lazy.ens_rps_statistic(p, t, e, pa, tb, self._fair, self._right_inclusive, bin_dim=self._bin_dim)
+
+  def _fused_field_per_variable(self, predictions, targets):
+    """The score at threshold fields as a lazy statistic that the Aggregator reduces with one launch of wbx_ens_rps_field_partial
+    (lazy.ens_rps_field_statistic), the fields gathered in place, or None where rps_field_route, the monotonicity that is asked
+    for, or the frame keep the host route."""
+    if not lazy.FUSED_ENS_RPS_FIELD:
+      return None
+    p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+    try:
+      fields = [v[da.name] if isinstance(v, xr.Dataset) else v for v, da in zip(self._thresholds, (p, t))]
+    except KeyError:
+      return None  # (the host route raises)
+    fields = [xr.as_dataarray(f) if isinstance(f, xr.DataArray) else f for f in fields]
+    route, how = rps_field_route(p, t, fields[0], fields[1], ensemble_dim=self._ensemble_dim, bin_dim=self._bin_dim,
+                                 skipna_ensemble=self._skipna_ensemble, fair=self._fair)
+    if route != 'fused':
+      return None
+    if self._enforce_monotonicity and not all(_strictly_increasing(f, self._bin_dim) for f in fields[:2 if how['stacked'] else 1]):
+      return None  # (the host route raises or not by the chunk's own selection)
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on (the host route says so where it needs one)
+      return None
+    if not engine.ens_rps_field_available(ctx):
+      return None
+    # A host-resident field behind a slab pool (a memory map, a very large array, climatology_cache.cached()) is gathered slab by
+    # slab like any climatology -- where there are slabs to select and one field serves both sides.  Without a time dim the pool has
+    # nothing to select along, and stacking two such fields would read them whole: both keep the host route.
+    from weatherbenchx_amd import climatology_cache  # pylint: disable=g-import-not-at-top
+    pooled = any(climatology_cache.cache_for(f) is not None for f in fields[:2 if how['stacked'] else 1])
+    if pooled and (how['stacked'] or not how['positions']):
+      return None
+    source = _stacked_fields(self.__dict__.setdefault('_field_stacks', {}), *fields) if how['stacked'] else fields[0]
+    try:
+      ref = base._aligned_ref(source, how['over_dims'], how['positions'])  # pylint: disable=protected-access
+      return lazy.ens_rps_field_statistic(p, t, self._ensemble_dim, ref, bin_dim=self._bin_dim, stacked=how['stacked'], fair=self._fair,
+                                          right_inclusive=self._right_inclusive, host=self.host_per_variable,
+                                          clim_key=(id(source), source.__dict__.get('_mutations', 0)))
+    except (ValueError, lazy._NeedsAlignment):  # pylint: disable=protected-access  (a frame the field does not broadcast against, a
+      return None  # slab pool built for another selection)
+
+
+def rps_field_route(predictions, targets, p_field, t_field, *, ensemble_dim: str, bin_dim: str, skipna_ensemble: bool, fair: bool):
+  """Where EnsembleRankedProbabilityScore at the threshold fields `p_field` / `t_field` (the variable's DataArrays) goes, decided
+  from labels, dims and dtypes alone (no device, no look at the values): ('fused', {'over_dims', 'positions', 'stacked'}) -- one
+  launch of wbx_ens_rps_field_partial, the fields gathered in place through `positions` (wrappers.bin_threshold_positions), `stacked`:
+  two different fields that are stacked along a new leading axis -- or ('host', the reason)."""
+  host = lambda why: ('host', why)
+  if skipna_ensemble:
+    return host('skipna_ensemble')
+  if not isinstance(p_field, xr.DataArray) or not isinstance(t_field, xr.DataArray):
+    return host('a side whose thresholds are not a field')
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  e = ensemble_dim
+  if e not in p.dims or e in t.dims:
+    return host('the member dim must be a dim of the predictions and not of the targets')
+  if bin_dim in p.dims or bin_dim in t.dims or not set(t.dims) <= set(p.dims):
+    return host('the frames of predictions and targets')
+  floats = ('float32', 'float64')
+  if any(str(a.dtype).replace('torch.', '') not in floats for a in (p, t, p_field, t_field)):
+    return host('dtypes other than float32 / float64')
+  m = p.sizes[e]
+  if m > _hip.ERPS_MAX_MEMBERS or (fair and m < 2):
+    return host(f'{m} members')
+  for f in (p_field, t_field):
+    if bin_dim not in f.dims or e in f.dims:
+      return host(f'a threshold field with dims {f.dims}')
+  k = p_field.sizes[bin_dim]
+  if not 1 <= k <= _hip.ERPS_MAX_THRESHOLDS or t_field.sizes[bin_dim] != k:
+    return host(f'{k} against {t_field.sizes[bin_dim]} thresholds')
+  labelled = [bin_dim in f.coords for f in (p_field, t_field)]
+  if labelled[0] != labelled[1] or (labelled[0] and not np.array_equal(np.asarray(p_field.coords[bin_dim].values),
+                                                                          np.asarray(t_field.coords[bin_dim].values))):
+    return host('bin labels that differ between the sides')  # (the host route joins them on the labels they share)
+  try:
+    over_p, pos_p = wrappers.bin_threshold_positions(p_field, p)
+    over_t, pos_t = wrappers.bin_threshold_positions(t_field, t)
+  except (KeyError, ValueError) as err:
+    return host(f'a selection that raises ({err})')  # (labels that are not found: the host route raises)
+  if over_p != over_t or set(pos_p) != set(pos_t) or any(not np.array_equal(pos_p[d], pos_t[d]) for d in pos_p):
+    return host('the two sides select different thresholds')
+  if p_field is t_field:
+    return 'fused', {'over_dims': over_p, 'positions': pos_p, 'stacked': False}
+  if p_field.dims != t_field.dims or p_field.shape != t_field.shape or str(p_field.dtype) != str(t_field.dtype):
+    return host('threshold fields that differ in dims, shape or dtype')
+  if set(p_field.coords) != set(t_field.coords) or any(
+      tuple(p_field.coords[c].dims) != tuple(t_field.coords[c].dims)
+      or not xr._values_equal(p_field._coords[c][1], t_field._coords[c][1]) for c in p_field.coords):  # pylint: disable=protected-access
+    return host('threshold fields that differ in coordinates')
+  # (one array behind two labelled objects -- the same variable of two Datasets -- is still one field)
+  return 'fused', {'over_dims': over_p, 'positions': pos_p, 'stacked': p_field.data is not t_field.data}
+
+
+def _strictly_increasing(field: xr.DataArray, bin_dim: str) -> bool:
+  """The whole field is free of NaN and strictly increasing along `bin_dim` (then every selection of it is), looked at once per
+  field object and state."""
+  memo = field.__dict__.setdefault('_wbx_rps_monotone', {})
+  key = (bin_dim, field.__dict__.get('_mutations', 0))
+  if key not in memo:
+    memo.clear()
+    values = np.moveaxis(np.asarray(field.values), field.dims.index(bin_dim), 0)
+    memo[key] = bool(not np.isnan(values).any() and (values.shape[0] < 2 or np.all(values[1:] > values[:-1])))
+  return memo[key]
+
+
+def _stacked_fields(cache: dict, p_field: xr.DataArray, t_field: xr.DataArray) -> xr.DataArray:
+  """[prediction thresholds, target thresholds] along a new leading axis (on the device for device payloads), built once per pair
+  of field objects and their states (`cache`: the statistic's, like SEEPS's device tables)."""
+  key = (id(p_field), id(t_field))
+  state = (p_field.__dict__.get('_mutations', 0), t_field.__dict__.get('_mutations', 0))
+  hit = cache.get(key)
+  if hit is None or hit[0] is not p_field or hit[1] is not t_field or hit[2] != state:
+    a, b = p_field.data, t_field.data
+    if xr._is_torch(a) or xr._is_torch(b):  # pylint: disable=protected-access
+      import torch  # pylint: disable=g-import-not-at-top
+      a = a if xr._is_torch(a) else torch.as_tensor(np.asarray(a), device=b.device)  # pylint: disable=protected-access
+      b = b if xr._is_torch(b) else torch.as_tensor(np.asarray(b), device=a.device)  # pylint: disable=protected-access
+      data = torch.stack([a, b.to(a.device)])
+    else:
+      data = np.stack([np.asarray(a), np.asarray(b)])
+    both = xr.DataArray(data, dims=(lazy.ERPSF_SIDE_DIM,) + tuple(p_field.dims), coords=dict(p_field._coords), _raw_coords=True,  # pylint: disable=protected-access
+                        name=p_field.name)
+    if len(cache) > 16:
+      cache.clear()
+    hit = cache[key] = (p_field, t_field, state, both)
+  return hit[3]
 
 
 def _fused_energy(lane: int, predictions, targets, dim, ensemble_dim: str, fair):

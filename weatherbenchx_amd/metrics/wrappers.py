@@ -392,9 +392,8 @@ IntersectPredictionAndTargetVariables = lambda metric: metric  # pylint: disable
 
 
 # ---- CDF / bin indicators, stacking, tiles --------------------------------------------------------------------------------------------
-def _take_along(da: xr.DataArray, dim: str, labels: np.ndarray, label_dims, label_coords) -> xr.DataArray:
-  """da.sel({dim: labels}) for an indexer of any rank: `dim` is replaced by `label_dims`; the labels stay as a coordinate `dim`."""
-  da = xr.as_dataarray(da)
+def _label_positions(da: xr.DataArray, dim: str, labels: np.ndarray) -> np.ndarray:
+  """The positions of `labels` (flattened) along `dim` of `da`; KeyError where a label is not found."""
   have = np.asarray(da.coords[dim].values)
   labels = np.asarray(labels)
   if have.dtype.kind in 'mM' or labels.dtype.kind in 'mM':
@@ -409,6 +408,14 @@ def _take_along(da: xr.DataArray, dim: str, labels: np.ndarray, label_dims, labe
   if not np.array_equal(have[idx], want.reshape(-1)):
     missing = want.reshape(-1)[have[idx] != want.reshape(-1)][:3]
     raise KeyError(f'not all values found in index {dim!r}: {missing}')
+  return idx
+
+
+def _take_along(da: xr.DataArray, dim: str, labels: np.ndarray, label_dims, label_coords) -> xr.DataArray:
+  """da.sel({dim: labels}) for an indexer of any rank: `dim` is replaced by `label_dims`; the labels stay as a coordinate `dim`."""
+  da = xr.as_dataarray(da)
+  labels = np.asarray(labels)
+  idx = _label_positions(da, dim, labels)
   axis = da.dims.index(dim)
   data = da.data
   if xr._is_torch(data):  # pylint: disable=protected-access
@@ -470,6 +477,57 @@ def select_bin_thresholds_by_time_from_chunk(bin_thresholds: xr.DataArray, chunk
         return _take_along(bt, 'dayofyear', _dayofyear(t), tdims, tcoords)
       return bt
   return bt
+
+
+def bin_threshold_positions(bin_thresholds: xr.DataArray, chunk: xr.DataArray):
+  """select_bin_thresholds_by_time_from_chunk as an index table: -> (over_dims, positions) with `positions` {dim of the thresholds:
+  int positions, shaped like the chunk's `over_dims`}, so that lazy.ClimatologyRef(bin_thresholds, over_dims, positions)
+  .aligned_view() holds the values of the selection (the chunk's time dims lead there, whatever their place in the selection).  No
+  time dim to select along: ((), {}).  Labels that are not found raise the selection's KeyError, and a sparse chunk (init_time and
+  lead_time on one dim) against thresholds with two dims to select along its ValueError."""
+  bt, chunk = xr.as_dataarray(bin_thresholds), xr.as_dataarray(chunk)
+  cc = chunk.coords
+
+  def coord(name):
+    c = cc[name]
+    return np.asarray(c.values), tuple(c.dims)
+
+  def table(over_dims, over_shape, **labels):  # dim -> (labels, their dims): every table broadcast over `over_dims`
+    out = {}
+    for dim, (lab, ldims) in labels.items():
+      pos = _label_positions(bt, dim, lab).reshape(np.asarray(lab).shape)
+      pos = pos.reshape([n if d in ldims else 1 for d, n in zip(over_dims, over_shape)])
+      out[dim] = np.ascontiguousarray(np.broadcast_to(pos, over_shape).astype(np.int64))
+    return tuple(over_dims), out
+  if 'init_time' in cc and 'lead_time' in cc:
+    (it, idims), (lt, ldims) = coord('init_time'), coord('lead_time')
+    if idims == ldims:  # sparse: both on one dim
+      valid, vdims = it + lt, idims
+    else:
+      valid, vdims = it[:, None] + lt[None, :], idims + ldims
+    for name in ('valid_time', 'time'):
+      if name in bt.dims:
+        return table(vdims, valid.shape, **{name: (valid, vdims)})
+    two = {'init_time', 'lead_time'} <= set(bt.dims) or {'dayofyear', 'lead_time'} <= set(bt.dims)
+    if two and idims == ldims:  # (the selection takes along one dim after the other and ends with that dim twice)
+      raise ValueError(f'duplicate dimension names: {idims + ldims}')
+    if {'init_time', 'lead_time'} <= set(bt.dims):
+      return table(vdims, valid.shape, init_time=(it, idims), lead_time=(lt, ldims))
+    if 'dayofyear' in bt.dims:
+      if 'lead_time' in bt.dims:
+        return table(vdims, valid.shape, dayofyear=(_dayofyear(it), idims), lead_time=(lt, ldims))
+      return table(vdims, valid.shape, dayofyear=(_dayofyear(valid), vdims))
+    return (), {}
+  for name in ('valid_time', 'time'):
+    if name in cc:
+      t, tdims = coord(name)
+      for tname in ('valid_time', 'time'):
+        if tname in bt.dims:
+          return table(tdims, t.shape, **{tname: (t, tdims)})
+      if 'dayofyear' in bt.dims:
+        return table(tdims, t.shape, dayofyear=(_dayofyear(t), tdims))
+      return (), {}
+  return (), {}
 
 
 def plain_thresholds(values):
