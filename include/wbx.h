@@ -877,7 +877,12 @@ int wbx_binned_atoms(wbx_ctx* ctx, const wbx_s1_plan* plan, int64_t nA, int64_t 
  * words (bins that are not boxes): when it is not zero use the two-stage route -- wbx_ens_binned would return NaN for the
  * cells of those patches.  wbx_ens_binned_atoms synchronises when overflow_out is not NULL.
  * Accuracy: as wbx_ens_partial (fp32 chain sums per point for M = 50 / 51, fp64 from the point's values on); lane 3 is formed
- * per (patch, bin) as lane 4 - lane 2 / M from the fp64 sums (the identity holds at every point). */
+ * per (patch, bin) as lane 4 - lane 2 / M from the fp64 sums (the identity holds at every point).  Every output against the float64
+ * restatement of the widened inputs: |d out| <= sum_i wt_i b_i + (N + 4) eps / 2 * sum_i |wt_i lane_i| over the N valid points of the
+ * cell inside the bin, b_i = the per-point bound of wbx_ens_partial for that M and eps = 2^-52, in any order of the sums (flushes,
+ * patches, the three levels, prepared tables or not); lane 3 takes lane 4's bound plus lane 2's / M; count lanes under dyadic weights
+ * are exact.  tests/test_gpu_ens_binned.py holds every output of every output mode (6 / 12 / 10 / 20 lanes), mask kind, register
+ * bucket, route and edge to that bound, computed per output from the inputs (tests/ens_binned_cases.py). */
 int wbx_ens_binned(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype, int M, int64_t member_stride, int algo, const void* p,
                    const void* t, const uint8_t* mask, const double* wt, const uint64_t* bits, int64_t nA, int64_t nBk,
                    int64_t nBr, int32_t w_on_x, int32_t nbin, const void* atoms, double* out);
