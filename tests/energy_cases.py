@@ -37,6 +37,12 @@ def relative_bound(m: int, l: int, dtype) -> float:
   return (l / 2.0 + 4.0) * unit(dtype) + (m * m + 4.0) * 2.0 ** -53
 
 
+def host_relative_bound(m: int, l: int, dtype) -> float:
+  """The host route's (labelled-array arithmetic in the input type): the same norms, (L / 2 + 4) u, then added in the input type too
+  -- M terms for the skill (M u more), M - 1 passes of M terms and the M - 1 pass sums for the spread (2 M u more)."""
+  return (l / 2.0 + 4.0 + 2.0 * m) * unit(dtype)
+
+
 def energy_points(p, t, fair):
   """p[M, frame..., L], t[frame..., L] -> stat[frame..., 2] in float64."""
   x = np.asarray(p).astype(np.float64)

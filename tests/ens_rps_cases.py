@@ -69,6 +69,27 @@ def rps_points(p, t, a, b, fair, right):
   return out
 
 
+def point_bound(stat):
+  """What a per-point value of rps_points can be off by: its one division (sum_k n_k is an exact integer), 2^-53 relatively; 0
+  where the value is NaN.  The kernel divides once per partial, after an exact integer sum: it has no per-point error at all."""
+  return np.where(np.isfinite(stat), 2.0 ** -53 * np.abs(stat), 0.0)
+
+
+def term_magnitudes(p, t, a, b, fair, right):
+  """Per point, sum_k of the absolute values of the terms whose difference is the score: (c_k / M - o_k)^2 and, when fair,
+  c_k (M - c_k) / (M^2 (M - 1)).  A route that forms the score from these in floating point, as the host route does, is accurate
+  relative to this sum and not to the score, which may be their exact cancellation (0 where no rounding at all would be allowed)."""
+  m = int(np.asarray(p).shape[0])
+  c = counts(p, a, right).astype(np.float64)
+  y = np.asarray(t).astype(np.float64)[..., None]
+  with np.errstate(invalid='ignore'):
+    o = ((y <= np.asarray(b, np.float64)) if right else (y < np.asarray(b, np.float64))).astype(np.float64)
+  terms = (c / m - o) ** 2
+  if fair:
+    terms = terms + c * (m - c) / float(m * m * (m - 1))
+  return terms.sum(axis=-1)
+
+
 def expected(p, t, a, b, fair, right, valid, flags, depth_chunk, x_kept):
   """-> (what stage 1 writes, [lead][chunk][lane][j]: the value lane, then the count lane under a mask and / or skipna; the
   statistic of every point as integers held in float64, NaN where it is NaN)."""

@@ -984,12 +984,20 @@ def norm_run(layout, dims, sizes):
   return length, live[0][1]
 
 
+def norm_run_order(layout, dims, sizes):
+  """The norm dims of more than one element in the order a run of this input walks them, the fastest first.  Element i of the run
+  of one input is element i of another's only where both walk the dims in the same order."""
+  return tuple(d for _, d in sorted((abs(layout.stride(d)), d) for d in dims if int(sizes[d]) != 1))
+
+
 def _enrg_operands(ctx, devs, func, ens, cat, mdim):
   if not 2 <= int(ens['M']) <= _hip.ENRG_MAX_MEMBERS:
     raise ValueError(f"one energy score launch takes 2..{_hip.ENRG_MAX_MEMBERS} members (got {ens['M']})")
   runs = [norm_run(devs[i].layout, ens['norm_dims'], ens['norm_sizes']) for i in (0, 1)]
   if runs[0] is None or runs[1] is None:
     raise ValueError(f"the norm dims {ens['norm_dims']} are not one strided run of the inputs as they are stored")
+  if len({norm_run_order(devs[i].layout, ens['norm_dims'], ens['norm_sizes']) for i in (0, 1)}) != 1:
+    raise ValueError(f"the two inputs store the norm dims {ens['norm_dims']} in different orders: their runs pair other elements")
   return _hip.ENRG_LANES, EnergyArgs(ens['M'], devs[0].layout.stride(mdim), runs[0][0], runs[0][1], runs[1][1]), None
 
 

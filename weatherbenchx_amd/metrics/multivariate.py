@@ -253,8 +253,9 @@ def _fused_energy(lane: int, predictions, targets, dim, ensemble_dim: str, fair)
   """The skill (lane 0) or spread (lane 1) of the energy score as a lazy statistic that the Aggregator reduces with
   wbx_ens_energy_partial (lazy.energy_statistic), or None where the host route has to do it: the switch is off, no device, other
   dtypes than float32 / float64, no member dim in the predictions or one in the targets, a norm dim that one input lacks, norm dims
-  that are not one strided run of an input as a launch sees it, targets with a dim of their own, nothing left of the frame, a
-  `mask` coordinate along a norm or member dim, or an ensemble size the kernel does not take."""
+  that are not one strided run of an input as a launch sees it or that the two inputs store in different orders (element i of one
+  run would not be element i of the other), targets with a dim of their own, nothing left of the frame, a `mask` coordinate along a
+  norm or member dim, or an ensemble size the kernel does not take."""
   if not lazy.FUSED_ENERGY:
     return None
   p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
@@ -274,6 +275,8 @@ def _fused_energy(lane: int, predictions, targets, dim, ensemble_dim: str, fair)
       return None
     if engine.norm_run(lazy.payload_layout(da), norm, da.sizes) is None:
       return None
+  if len({engine.norm_run_order(lazy.payload_layout(da), norm, da.sizes) for da in (p, t)}) != 1:
+    return None
   try:
     ctx = _hip.default_context()
   except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
