@@ -268,12 +268,13 @@ class _FssPlanOnDevice:
 _fss_plan_cache: dict = {}
 
 
-def _fss_planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, wrap_longitude):
+def _fss_planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, cat):
   """(the S1Plan stage 2 sees, the device wbx_fss_plan) through a cheap signature, like _planned_inner: steady-state chunks skip
-  table building and uploads.  `layouts` = the engine's four (p, t, -, mask)."""
+  table building and uploads.  `layouts` = the engine's four (p, t, -, mask); `cat`: the launch's, for 'wrap_longitude'."""
+  wrap_longitude = bool(cat.get('wrap_longitude', False))
   sig = (id(ctx), tuple(dims), tuple(sizes[d] for d in dims),
          tuple(None if l is None else (tuple(sorted(l.strides.items(), key=str)), l.itemsize) for l in layouts),
-         tuple(sorted(reduce_dims, key=str)), tuple(sorted(wdep, key=str)), flags, bool(wrap_longitude))
+         tuple(sorted(reduce_dims, key=str)), tuple(sorted(wdep, key=str)), flags, wrap_longitude)
   hit = _fss_plan_cache.get(sig)
   if hit is None:
     fplan = planner.build_fss_plan(dims, sizes, [layouts[0], layouts[1], layouts[3]], reduce_dims, wdep_dims=wdep, flags=flags,
@@ -383,7 +384,7 @@ def _planned_inner(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, f
   hit = _fast_plan_cache.get(sig)
   if hit is None:
     plan = planner.build_s1_plan(dims, sizes, layouts, reduce_dims, wdep_dims=wdep, gather=gather, flags=flags,
-                                 allow_vec4=(kind in ('det', 'cont') and x_weights is None and force_x is None), force_x_dim=force_x,
+                                 allow_vec4=(_KINDS[kind].vec4 and x_weights is None and force_x is None), force_x_dim=force_x,
                                  fold_x=False if x_weights is None else
                                  (True if kind == 'det' else ('point64' if one_wave else 'point')))
     if kind == 'cont' and plan.plane_rows > 0:  # 16-byte loads yes, plane mode no: wbx_contingency_partial walks rows
@@ -465,148 +466,43 @@ def _scratch(ctx, slot: str, nbytes: int):
   return buf
 
 
-def _threshold_table(ctx, thresholds):
-  """The device copy of a float64 threshold table, uploaded once per (device, contents)."""
-  tkey = (ctx.device_id, np.asarray(thresholds, np.float64).tobytes())
-  thr = _thr_cache.get(tkey)
-  if thr is None:
-    if len(_thr_cache) > 64:
-      _thr_cache.clear()
-    thr = _thr_cache[tkey] = ctx.upload(np.asarray(thresholds, np.float64))
-  return thr
-
-
-def _slot_table(ctx, slots):
-  """The device copy of an int32 table of (lo, hi) count runs (wbx_ens_prob_contingency_partial), uploaded once per (device, contents)."""
-  slots = np.ascontiguousarray(slots, np.int32)
-  tkey = (ctx.device_id, 'i32', slots.tobytes())
+def _const_table(ctx, values, dtype=np.float64):
+  """The device copy of a constant table -- float64 thresholds, the int32 (lo, hi) count runs of wbx_ens_prob_contingency_partial --
+  uploaded once per (device, dtype, contents)."""
+  values = np.ascontiguousarray(values, dtype)
+  tkey = (ctx.device_id, values.dtype.str, values.tobytes())
   buf = _thr_cache.get(tkey)
   if buf is None:
     if len(_thr_cache) > 64:
       _thr_cache.clear()
-    buf = _thr_cache[tkey] = ctx.upload(slots)
+    buf = _thr_cache[tkey] = ctx.upload(values)
   return buf
 
 
-def contingency_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_contingency_partial: a real library context whose library exports the entry point.  Any
-  other context object (the NumPy plan interpreter of the CPU tests has no library) keeps the host route."""
+def _entry_available(ctx, *symbols) -> bool:
+  """Whether `ctx` can launch the entry points `symbols`: a real library context whose library exports them.  Any other context
+  object (the NumPy plan interpreter of the CPU tests has no library) keeps the host route."""
   if not isinstance(ctx, _hip.Context):
     return False
   try:
-    return getattr(ctx.lib, 'wbx_contingency_partial', None) is not None
+    return all(getattr(ctx.lib, s, None) is not None for s in symbols)
   except AttributeError:
     return False
 
 
-def ens_rps_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_rps_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_rps_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_rps_field_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_rps_field_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_rps_field_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_energy_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_energy_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_energy_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_variogram_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_variogram_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_variogram_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_wasserstein_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_wasserstein_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_wasserstein_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_interval_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_interval_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_interval_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def ens_prob_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_prob_contingency_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_prob_contingency_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def brier_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_ens_brier_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_ens_brier_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def seeps_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_seeps_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_seeps_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def fss_thresholds_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_fss_threshold_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_fss_threshold_partial', None) is not None
-  except AttributeError:
-    return False
-
-
-def fss_available(ctx) -> bool:
-  """Whether `ctx` can launch wbx_fss_partial (see contingency_available)."""
-  if not isinstance(ctx, _hip.Context):
-    return False
-  try:
-    return getattr(ctx.lib, 'wbx_fss_partial', None) is not None
-  except AttributeError:
-    return False
+# the gates of the fused statistics (metrics/*.py and lazy.py look them up through the module at call time; tests patch them)
+contingency_available = lambda ctx: _entry_available(ctx, 'wbx_contingency_partial')
+ens_rps_available = lambda ctx: _entry_available(ctx, 'wbx_ens_rps_partial')
+ens_rps_field_available = lambda ctx: _entry_available(ctx, 'wbx_ens_rps_field_partial')
+ens_energy_available = lambda ctx: _entry_available(ctx, 'wbx_ens_energy_partial')
+ens_variogram_available = lambda ctx: _entry_available(ctx, 'wbx_ens_variogram_partial')
+ens_wasserstein_available = lambda ctx: _entry_available(ctx, 'wbx_ens_wasserstein_partial')
+ens_interval_available = lambda ctx: _entry_available(ctx, 'wbx_ens_interval_partial')
+ens_prob_available = lambda ctx: _entry_available(ctx, 'wbx_ens_prob_contingency_partial')
+brier_available = lambda ctx: _entry_available(ctx, 'wbx_ens_brier_partial')
+seeps_available = lambda ctx: _entry_available(ctx, 'wbx_seeps_partial')
+fss_thresholds_available = lambda ctx: _entry_available(ctx, 'wbx_fss_threshold_partial')
+fss_available = lambda ctx: _entry_available(ctx, 'wbx_fss_partial')
 
 
 def new_context() -> _hip.Context:
@@ -900,41 +796,52 @@ _table_ptr = lambda buf: C.c_void_p(buf.ptr) if buf is not None else None
 
 
 def _cat_operands(ctx, devs, func, ens, cat, mdim):
+  """Indicator statistics: `cat` = {'func', 'ncat', 'thresholds' (float64 ndarray or None), 'member_dim' (or None), 'M'[, 'thr_field',
+  'cat_dim': thresholds that depend on the statistic's dims, input 2]}; one value lane per category."""
   field = cat.get('thr_field') is not None
-  thr = _threshold_table(ctx, cat['thresholds']) if cat.get('thresholds') is not None and not field else None
+  thr = _const_table(ctx, cat['thresholds']) if cat.get('thresholds') is not None and not field else None
   return int(cat['ncat']), None, CatArgs(cat['func'], int(cat['ncat']), cat.get('M', 1) if mdim else 1,
                                          devs[0].layout.stride(mdim) if mdim else 0, thr,
                                          devs[2].layout.stride(cat['cat_dim']) if field else None)
 
 
 def _cont_operands(ctx, devs, func, ens, cat, mdim):
+  """Thresholded contingency tables: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
+  cell * nthr + k, cell in (TP, FP, FN, TN)."""
   nthr = int(np.asarray(cat['thresholds']).size)
   if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
     raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
-  return _hip.CONT_CELLS * nthr, None, ContArgs(nthr, _threshold_table(ctx, cat['thresholds']))
+  return _hip.CONT_CELLS * nthr, None, ContArgs(nthr, _const_table(ctx, cat['thresholds']))
+
+
+def _check_ranges(what, count_ok, counts, ens, max_members):
+  """The two refusals 'erps', 'erpsf' and 'epc' share, in their order: the number of thresholds (`counts`: the words after the
+  '1..'), then the number of members."""
+  if not count_ok:
+    raise ValueError(f'one {what}launch takes 1..{counts}')
+  if not 1 <= int(ens['M']) <= max_members:
+    raise ValueError(f"one {what}launch takes 1..{max_members} members (got {ens['M']})")
 
 
 def _erps_operands(ctx, devs, func, ens, cat, mdim):
-  nthr = int(np.asarray(cat['p_thresholds']).size)
-  if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS or int(np.asarray(cat['t_thresholds']).size) != nthr:
-    raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} prediction and as many target thresholds '
-                     f"(got {nthr} and {int(np.asarray(cat['t_thresholds']).size)})")
-  if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
-    raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
+  """Ranked probability score of an ensemble: `cat` = {'p_thresholds', 't_thresholds' (float64 ndarrays of equal size, at most
+  _hip.ERPS_MAX_THRESHOLDS), 'right_inclusive'}, `ens` = {'member_dim', 'M', 'fair'}; one value lane."""
+  nthr, nt = int(np.asarray(cat['p_thresholds']).size), int(np.asarray(cat['t_thresholds']).size)
+  _check_ranges('ensemble RPS ', 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS and nt == nthr,
+                f'{_hip.ERPS_MAX_THRESHOLDS} prediction and as many target thresholds (got {nthr} and {nt})', ens, _hip.ERPS_MAX_MEMBERS)
   return 1, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), RpsArgs(
-      nthr, _threshold_table(ctx, cat['p_thresholds']), _threshold_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
+      nthr, _const_table(ctx, cat['p_thresholds']), _const_table(ctx, cat['t_thresholds']), bool(cat['right_inclusive']))
 
 
 def _erpsf_operands(ctx, devs, func, ens, cat, mdim):
-  """`cat` = {'bin_dim', 'nthr', 'side_dim' (the dim two stacked fields lie along, prediction first, or None: one field for both
-  sides), 'right_inclusive'}; the threshold field is input 2, in its own dtype."""
+  """The same score at threshold fields: inputs (p, t, threshold field behind `gather`), `cat` = {'bin_dim', 'nthr', 'side_dim' (the
+  dim two stacked fields lie along, prediction first, or None: one field for both sides), 'right_inclusive'}, `ens` as for 'erps';
+  the field stays in its own dtype -- the kernel compares as NumPy promotes."""
   if devs[2] is None:
     raise ValueError('the ensemble RPS at threshold fields needs the field (input 2)')
   nthr = int(cat['nthr'])
-  if not 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS:
-    raise ValueError(f'one ensemble RPS launch takes 1..{_hip.ERPS_MAX_THRESHOLDS} thresholds (got {nthr})')
-  if not 1 <= int(ens['M']) <= _hip.ERPS_MAX_MEMBERS:
-    raise ValueError(f"one ensemble RPS launch takes 1..{_hip.ERPS_MAX_MEMBERS} members (got {ens['M']})")
+  _check_ranges('ensemble RPS ', 1 <= nthr <= _hip.ERPS_MAX_THRESHOLDS, f'{_hip.ERPS_MAX_THRESHOLDS} thresholds (got {nthr})',
+                ens, _hip.ERPS_MAX_MEMBERS)
   lay = devs[2].layout
   thr_stride = lay.stride(cat['bin_dim']) if nthr > 1 else (lay.stride(cat['bin_dim']) or 1)
   t_off = lay.stride(cat['side_dim']) if cat.get('side_dim') else 0
@@ -943,19 +850,22 @@ def _erpsf_operands(ctx, devs, func, ens, cat, mdim):
 
 
 def _epc_operands(ctx, devs, func, ens, cat, mdim):
+  """Contingency tables of ensemble event probabilities: `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag)},
+  `cat` = {'thresholds': float64 ndarray of K event thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts},
+  K * J <= _hip.EPC_MAX_PAIRS; value lane cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN)."""
   thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
   slots = np.asarray(cat['slots'], np.int32).reshape(-1, 2)
   nthr, nslot = int(thr.size), int(slots.shape[0])
-  if nthr < 1 or nslot < 1 or nthr * nslot > _hip.EPC_MAX_PAIRS:
-    raise ValueError(f'one launch takes 1..{_hip.EPC_MAX_PAIRS} (event threshold, probability slot) pairs (got {nthr} x {nslot})')
-  if not 1 <= int(ens['M']) <= _hip.EPC_MAX_MEMBERS:
-    raise ValueError(f"one launch takes 1..{_hip.EPC_MAX_MEMBERS} members (got {ens['M']})")
+  _check_ranges('', 1 <= nthr * nslot <= _hip.EPC_MAX_PAIRS,
+                f'{_hip.EPC_MAX_PAIRS} (event threshold, probability slot) pairs (got {nthr} x {nslot})', ens, _hip.EPC_MAX_MEMBERS)
   return _hip.EPC_CELLS * nthr * nslot, RpsEnsArgs(ens['M'], devs[0].layout.stride(mdim)), EpcArgs(
-      nthr, _threshold_table(ctx, thr), nslot, _slot_table(ctx, slots))
+      nthr, _const_table(ctx, thr), nslot, _const_table(ctx, slots, np.int32))
 
 
 def _brier_operands(ctx, devs, func, ens, cat, mdim):
-  """`ens` = {'member_dim', 'M', 'fair': False} or None (a deterministic pair: M = 1), `cat` = {'thresholds', 'denom'}."""
+  """Error, AbsoluteError and SquaredError of event probabilities: `ens` = {'member_dim', 'M', 'fair': False} or None (a
+  deterministic pair: M = 1), `cat` = {'thresholds': float64 ndarray of at most _hip.BRIER_MAX_THRESHOLDS, 'denom': M or M + 1, 1
+  without a member dim}; value lane stat * K + k, stat in (Error, AbsoluteError, SquaredError)."""
   thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
   nthr, m, denom = int(thr.size), int(ens['M']) if ens else 1, int(cat['denom'])
   if not 1 <= nthr <= _hip.BRIER_MAX_THRESHOLDS:
@@ -965,8 +875,8 @@ def _brier_operands(ctx, devs, func, ens, cat, mdim):
   if denom != 1 if (mdim is None or m == 1) else denom not in (m, m + 1):
     raise ValueError(f'the denominator of a Brier launch is M or M + 1, and 1 for one member or none (got {denom} for M = {m})')
   if mdim is None:  # one "member": the entry ignores the stride
-    return _hip.BRIER_STATS * nthr, BrierEnsArgs(1, 0, 1), ContArgs(nthr, _threshold_table(ctx, thr))
-  return _hip.BRIER_STATS * nthr, BrierEnsArgs(m, devs[0].layout.stride(mdim), denom), ContArgs(nthr, _threshold_table(ctx, thr))
+    return _hip.BRIER_STATS * nthr, BrierEnsArgs(1, 0, 1), ContArgs(nthr, _const_table(ctx, thr))
+  return _hip.BRIER_STATS * nthr, BrierEnsArgs(m, devs[0].layout.stride(mdim), denom), ContArgs(nthr, _const_table(ctx, thr))
 
 
 def norm_run(layout, dims, sizes):
@@ -991,6 +901,8 @@ def norm_run_order(layout, dims, sizes):
 
 
 def _enrg_operands(ctx, devs, func, ens, cat, mdim):
+  """Energy score of an ensemble: `ens` = {'member_dim', 'M', 'fair', 'norm_dims', 'norm_sizes'}, `dims` without the member dim and
+  the norm dims, which must be one strided run of both inputs; value lanes skill, spread."""
   if not 2 <= int(ens['M']) <= _hip.ENRG_MAX_MEMBERS:
     raise ValueError(f"one energy score launch takes 2..{_hip.ENRG_MAX_MEMBERS} members (got {ens['M']})")
   runs = [norm_run(devs[i].layout, ens['norm_dims'], ens['norm_sizes']) for i in (0, 1)]
@@ -1002,6 +914,9 @@ def _enrg_operands(ctx, devs, func, ens, cat, mdim):
 
 
 def _vgrm_operands(ctx, devs, func, ens, cat, mdim):
+  """Variogram score of an ensemble: `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag), 'norm_dims' (the
+  score's one dim), 'norm_sizes', 'power'}, `dims` without the member dim and that dim, which must be one strided run of both
+  inputs; one value lane."""
   if not 1 <= int(ens['M']) <= _hip.VGRAM_MAX_MEMBERS:
     raise ValueError(f"one variogram score launch takes 1..{_hip.VGRAM_MAX_MEMBERS} members (got {ens['M']})")
   if float(ens['power']) not in _hip.VGRAM_POWERS:
@@ -1016,6 +931,8 @@ def _vgrm_operands(ctx, devs, func, ens, cat, mdim):
 
 
 def _wass_operands(ctx, devs, func, ens, cat, mdim):
+  """Wasserstein-1 distance between two ensembles: `ens` = {'member_dim' (a dim of both inputs), 'M', 'N', 'fair': False (the entry
+  takes no such flag)}, 1 <= M, N <= _hip.WASS_MAX_MEMBERS; one value lane."""
   for side in ('M', 'N'):
     if not 1 <= int(ens[side]) <= _hip.WASS_MAX_MEMBERS:
       raise ValueError(f"one Wasserstein distance launch takes 1..{_hip.WASS_MAX_MEMBERS} members a side (got {ens['M']}, {ens['N']})")
@@ -1034,6 +951,10 @@ def ivl_bound(q, m: int):
 
 
 def _ivl_operands(ctx, devs, func, ens, cat, mdim):
+  """Interval statistics of an ensemble: `ens` = {'member_dim', 'M', 'fair': False}, `cat` = {'lanes' (a set of _hip.IVL_* bits),
+  'params': {bit: {'bounds': (q_lo, q_hi), 'threshold', 'q_index': positions of the two levels along the climatology's quantile
+  dim}}, 'quantile_dim'}, inputs (p, t[, climatology]) with the climatology behind `gather` like ACC's; one value lane per bit
+  set, in the order Covered, Confident, JaccardDistant."""
   m = int(ens['M'])
   if not 1 <= m <= _hip.IVL_MAX_MEMBERS:
     raise ValueError(f'one interval statistics launch takes 1..{_hip.IVL_MAX_MEMBERS} members (got {m})')
@@ -1071,8 +992,9 @@ def place_block(strides: dict, sizes: dict, place_dims):
 
 
 def _seeps_operands(ctx, devs, func, ens, cat, mdim):
-  """`cat` = {'dry_threshold', 'table' (float64 [3, 3, *place shape], categorical.seeps_score_table), 'place_dims', 'device_tables'
-  (a dict the caller keeps: one upload per device and layout)}.  The table goes up with the strides the wet thresholds' device
+  """SEEPS from a per-place score table: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table'
+  (float64 [3, 3, *place shape], categorical.seeps_score_table), 'place_dims', 'device_tables' (a dict the caller keeps: one upload
+  per device and layout)}; one value lane.  The table goes up with the strides the wet thresholds' device
   layout has along the place dims, cell by cell: the kernel reads cell c of a point at input 2's ungathered address + c * block."""
   if devs[2] is None:
     raise ValueError('SEEPS needs the wet thresholds (input 2)')
@@ -1094,9 +1016,11 @@ def _seeps_operands(ctx, devs, func, ens, cat, mdim):
 
 
 def _fss_operands(ctx, devs, func, ens, cat, mdim):
-  """`cat` = {'n': the neighbourhood size of this launch, 'wrap_longitude'[, 'thresholds': float64 ndarray of at most
-  _hip.FSS_THR_MAX: the inputs are continuous fields, value lane 3 k + term (wbx_fss_threshold_partial)]}; raises what the launch
-  would refuse."""
+  """The three terms of the fractions skill score at ONE neighbourhood size: inputs (p, t) over one frame with `latitude` and
+  `longitude`, `cat` = {'n': the size of this launch, 'wrap_longitude'[, 'thresholds': float64 ndarray of at most _hip.FSS_THR_MAX:
+  the inputs are CONTINUOUS fields and (p > thr_k, t > thr_k) are scored, value lane 3 k + term (wbx_fss_threshold_partial)]}, `mask`
+  the mask of the statistic for that size; value lanes (Pf - Tf)^2, Pf^2, Tf^2.  The plan is planner.build_fss_plan's (`_fss_planned`):
+  x is longitude, latitude is the last key dim whatever the weights depend on, planner.FssPlanError where it cannot be."""
   n = int(cat['n'])
   if n < 1 or n % 2 != 1:
     raise ValueError('neighborhood_size must be odd.')
@@ -1105,17 +1029,24 @@ def _fss_operands(ctx, devs, func, ens, cat, mdim):
   thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
   if not 1 <= int(thr.size) <= _hip.FSS_THR_MAX:
     raise ValueError(f'one thresholded FSS call takes 1..{_hip.FSS_THR_MAX} thresholds (got {thr.size})')
-  return _hip.FSS_LANES * int(thr.size), None, FssArgs(n, int(thr.size), _threshold_table(ctx, thr))
+  return _hip.FSS_LANES * int(thr.size), None, FssArgs(n, int(thr.size), _const_table(ctx, thr))
 
 
 # kind -> operands(ctx, devs, func, ens, cat, member_dim) -> (value lanes, the `ens` tuple, the `cat` tuple), raising what the
 #           launch would refuse;  keep: the device buffers among the `cat` tuple's fields (a recorded chunk holds them);
 #         call(d, out, dtype, func, ens, cat) -> (library function, its arguments behind ctx and plan), d[i] = pointer of input i;
-#           the `ens` tuple goes in as it stands (its fields are the entry's integers, in the entry's order)
-_Kind = collections.namedtuple('_Kind', 'operands keep call')
+#           the `ens` tuple goes in as it stands (its fields are the entry's integers, in the entry's order);
+#         vec4: the entry has 16-byte loads (planner.build_s1_plan's allow_vec4);  own_dtype2: input 2 goes to the device in its own
+#           dtype, not the inputs' common one;  keep2: input 2 is the same array chunk after chunk even without a gather table (a
+#           recorded chunk holds it);  planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, cat) -> (plan, device plan) where
+#           the entry has a plan struct of its own (None: _planned)
+# What `ens` / `cat` of reduce_statistics hold for a kind is in the docstring of its operands function; every kind but 'det' and
+# 'ens' always runs stage 1, then wbx_contract / wbx_contract_bits: no folded x weights, no binned route.  lazy._LAZY_KINDS has the
+# same keys: what FusedGroup does per kind.
+_Kind = collections.namedtuple('_Kind', 'operands keep call vec4 own_dtype2 keep2 planned', defaults=(False, False, False, None))
 _KINDS = {
     'det': _Kind(lambda ctx, devs, func, ens, cat, mdim: (_hip.DET_LANES[func], None, None), (),
-                 lambda d, out, dt, func, ens, cat: ('wbx_det_partial', (func, dt, d[0], d[1], d[2], d[3], out))),
+                 lambda d, out, dt, func, ens, cat: ('wbx_det_partial', (func, dt, d[0], d[1], d[2], d[3], out)), vec4=True),
     'ens': _Kind(lambda ctx, devs, func, ens, cat, mdim:
                  (_hip.ENS_LANES, EnsArgs(ens['M'], devs[0].layout.stride(mdim), ens['algo']), None), (),
                  lambda d, out, dt, func, ens, cat: ('wbx_ens_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),
@@ -1130,7 +1061,7 @@ _KINDS = {
                                       d[3], out))),
     'cont': _Kind(_cont_operands, ('thr',),
                   lambda d, out, dt, func, ens, cat:
-                  ('wbx_contingency_partial', (dt, int(cat.nthr), d[0], d[1], _table_ptr(cat.thr), d[3], out))),
+                  ('wbx_contingency_partial', (dt, int(cat.nthr), d[0], d[1], _table_ptr(cat.thr), d[3], out)), vec4=True),
     'erps': _Kind(_erps_operands, ('p_thr', 't_thr'),
                   lambda d, out, dt, func, ens, cat:
                   ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
@@ -1138,7 +1069,8 @@ _KINDS = {
     'erpsf': _Kind(_erpsf_operands, (),  # (the threshold field is input 2: kept like a climatology behind a gather table)
                    lambda d, out, dt, func, ens, cat:
                    ('wbx_ens_rps_field_partial', (dt, int(cat.thr_dtype), *map(int, ens), int(cat.nthr), int(cat.thr_stride),
-                                                  int(cat.t_off), int(bool(cat.right)), d[0], d[1], d[2], d[3], out))),
+                                                  int(cat.t_off), int(bool(cat.right)), d[0], d[1], d[2], d[3], out)),
+                   own_dtype2=True, keep2=True),
     'epc': _Kind(_epc_operands, ('thr', 'slots'),
                  lambda d, out, dt, func, ens, cat:
                  ('wbx_ens_prob_contingency_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), int(cat.nslot),
@@ -1162,7 +1094,8 @@ _KINDS = {
     'fss': _Kind(_fss_operands, ('thr',),
                  lambda d, out, dt, func, ens, cat:
                  ('wbx_fss_threshold_partial', (dt, int(cat.n), int(cat.nthr), _table_ptr(cat.thr), d[0], d[1], d[3], out))
-                 if cat.thr is not None else ('wbx_fss_partial', (dt, int(cat.n), d[0], d[1], d[3], out))),
+                 if cat.thr is not None else ('wbx_fss_partial', (dt, int(cat.n), d[0], d[1], d[3], out)),
+                 planned=_fss_planned),  # the stencil's own plan; `plan` is how stage 2 sees its partial (planner.build_fss_plan)
 }
 
 
@@ -1861,41 +1794,9 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
                       w_da: xr.DataArray | None, bin_dims: Sequence, *, func: int = 0, mask: xr.DataArray | None = None,
                       skipna: bool = False, gather: planner.GatherSpec | None = None, ens=None, cat=None,
                       ctx: _hip.Context | None = None):
-  """Fused statistics + weighted/binned reduction.
-
-  kind 'det' / 'ens' / 'cat' (indicator statistics: `cat` = {'func', 'ncat', 'thresholds' (float64 ndarray or None),
-  'member_dim' (or None), 'M'}; one value lane per category) / 'cont' (thresholded contingency tables,
-  wbx_contingency_partial: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
-  cell * nthr + k, cell in (TP, FP, FN, TN)) / 'erps' (ranked probability score of an ensemble, wbx_ens_rps_partial: `cat` =
-  {'p_thresholds', 't_thresholds' (float64 ndarrays of equal size, at most _hip.ERPS_MAX_THRESHOLDS), 'right_inclusive'},
-  `ens` = {'member_dim', 'M', 'fair'}; one value lane; always stage 1, then wbx_contract / wbx_contract_bits) / 'erpsf' (the same
-  score at threshold fields, wbx_ens_rps_field_partial: inputs (p, t, threshold field behind `gather`, in its own dtype), `cat` =
-  {'bin_dim', 'nthr', 'side_dim' (of two stacked fields, or None), 'right_inclusive'}, `ens` as for 'erps'; the same stage 2) / 'enrg' (energy
-  score of an ensemble, wbx_ens_energy_partial: `ens` = {'member_dim', 'M', 'fair', 'norm_dims', 'norm_sizes'}, `dims` without the
-  member dim and the norm dims, which must be one strided run of both inputs; value lanes skill, spread; always stage 1, then
-  wbx_contract / wbx_contract_bits: no folded x weights, no binned route) / 'vgrm' (variogram score of an ensemble,
-  wbx_ens_variogram_partial: `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag), 'norm_dims' (the score's one
-  dim), 'norm_sizes', 'power'}, `dims` without the member dim and that dim, which must be one strided run of both inputs; one
-  value lane; the same stage 2) / 'wass' (Wasserstein-1 distance between two ensembles, wbx_ens_wasserstein_partial: `ens` =
-  {'member_dim' (a dim of both inputs), 'M', 'N', 'fair': False (the entry takes no such flag)}, 1 <= M, N <= _hip.WASS_MAX_MEMBERS; one
-  value lane; the same stage 2) / 'ivl' (interval statistics of an ensemble, wbx_ens_interval_partial: `ens` = {'member_dim', 'M',
-  'fair': False}, `cat` = {'lanes' (a set of _hip.IVL_* bits), 'params': {bit: {'bounds': (q_lo, q_hi), 'threshold', 'q_index':
-  positions of the two levels along the climatology's quantile dim}}, 'quantile_dim'}, inputs (p, t[, climatology]) with the
-  climatology behind `gather` like ACC's; one value lane per bit set, in the order Covered, Confident, JaccardDistant; the same
-  stage 2) / 'epc' (contingency tables of ensemble event probabilities, wbx_ens_prob_contingency_partial: the operands of 'erps' --
-  `ens` = {'member_dim', 'M', 'fair': False (the entry takes no such flag)} --, `cat` = {'thresholds': float64 ndarray of K event
-  thresholds, 'slots': int32 ndarray [J, 2] of (lo, hi) runs of member counts}, K * J <= _hip.EPC_MAX_PAIRS; value lane
-  cell * (K * J) + k * J + j, cell in (TP, FP, FN, TN); the same stage 2) / 'brier' (Error, AbsoluteError and SquaredError of event
-  probabilities, wbx_ens_brier_partial: `ens` = {'member_dim', 'M', 'fair': False} or None for a deterministic pair, `cat` =
-  {'thresholds': float64 ndarray of at most _hip.BRIER_MAX_THRESHOLDS, 'denom': M or M + 1, 1 without a member dim}; value lane
-  stat * K + k, stat in (Error, AbsoluteError, SquaredError); the same stage 2) / 'seeps' (SEEPS from a per-place score table,
-  wbx_seeps_partial: inputs (p, t, wet-threshold climatology behind `gather`), `cat` = {'dry_threshold', 'table' (float64
-  [3, 3, *place shape]), 'place_dims', 'device_tables'}; one value lane; the same stage 2) / 'fss' (the three terms of the fractions
-  skill score at ONE neighbourhood size, wbx_fss_partial: inputs (p, t) over one frame with `latitude` and `longitude`, `cat` = {'n',
-  'wrap_longitude'}, `mask` the mask of the statistic for that size; with 'thresholds' (float64 ndarray of at most _hip.FSS_THR_MAX) in
-  `cat` the inputs are CONTINUOUS fields and wbx_fss_threshold_partial scores (p > thr_k, t > thr_k): value lane 3 k + term; the plan is planner.build_fss_plan's -- x is longitude, latitude
-  is the last key dim whatever the weights depend on, planner.FssPlanError where it cannot be --; value lanes (Pf - Tf)^2, Pf^2, Tf^2;
-  the same stage 2).
+  """Fused statistics + weighted/binned reduction of `inputs` = (p, t[, input 2: a climatology or a field behind `gather`]) over
+  the frame `dims` / `sizes`.  `kind` is a key of `_KINDS`: its row names the entry point, and the docstring of its operands function
+  says what `ens` and `cat` hold for it and what its value lanes are.
 
   Returns (values, counts, out_dims): `values` is ONE array (lanes,) + out_dims, out_dims =
   (A dims..., Bk dims..., [x dim], bin dims...) -- a view of the kernel's output, so `values[lane]` is a view too;
@@ -1911,13 +1812,13 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
     if twin is not None:
       return twin
   ctx = ctx or _launch_context(kind)
+  row = _KINDS[kind]
   wdep = set(w_da.dims) - set(bin_dims) if w_da is not None else set()
   member_dim = ens['member_dim'] if ens else (cat.get('member_dim') if cat else None)
   datas = [i.data if i is not None else None for i in inputs]
-  # (kind 'erpsf': the threshold field, input 2, stays in its own type -- the kernel compares as NumPy promotes)
-  dtype_code = _common_dtype(datas[:2] if kind == 'erpsf' else datas)
+  dtype_code = _common_dtype(datas[:2] if row.own_dtype2 else datas)
   _sync_torch_producers(datas)
-  devs = [(_to_device(ctx, i, own_dtype(i) if (kind == 'erpsf' and k == 2) else dtype_code) if i is not None else None)
+  devs = [(_to_device(ctx, i, own_dtype(i) if (row.own_dtype2 and k == 2) else dtype_code) if i is not None else None)
           for k, i in enumerate(inputs)]
   while len(devs) < 4:
     devs.append(None)
@@ -1960,10 +1861,10 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
         x_weights, wdep, w_da = xw, set(), None
       else:
         hit = None
-  if kind == 'fss':  # the stencil's own plan; `plan` is how stage 2 sees its partial (planner.build_fss_plan)
-    hit = _fss_planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, bool(cat.get('wrap_longitude', False)))
+  if row.planned is not None:
+    hit = row.planned(ctx, dims, sizes, layouts, reduce_dims, wdep, flags, cat)
   plan, dplan = hit if hit is not None else _planned(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, flags)
-  nl, ens_args, cat_args = _KINDS[kind].operands(ctx, devs, func, ens, cat, member_dim)
+  nl, ens_args, cat_args = row.operands(ctx, devs, func, ens, cat, member_dim)
   counted = bool(flags & 3)
   shared_count = counted and not (flags & _hip.FLAG_SKIPNA)  # mask only: one count lane for every statistic
   nl_total = nl + 1 if shared_count else nl * (2 if counted else 1)
@@ -1972,8 +1873,8 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   #  tables, inputs that do not follow the chunk such as the climatology, threshold tables)
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
-  replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in _KINDS[kind].keep),
-              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None or kind == 'erpsf')) else None,
+  replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in row.keep),
+              devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None or row.keep2)) else None,
               # (a mask that outlives the chunk: the places whose dry fraction is in range, kind 'seeps')
               devs[3] if (mask is not None and cat and cat.get('mask_da') is mask) else None)
   bin_shape = w_buf.bin_shape

@@ -10,6 +10,7 @@ all lanes at once, which is one stage-1 launch that reads every input exactly on
 """
 from __future__ import annotations
 
+import collections
 import os
 import weakref
 from typing import Sequence
@@ -227,6 +228,23 @@ def _reduce_in_blocks(subs, reduce_one, join):
   return join(values), join(counts), out_dims
 
 
+def _reduce_threshold_blocks(launch, thr, ngroup: int, block: int, **extra):
+  """Statistics whose lanes are `ngroup` groups of one lane per threshold, lane g * K + k (the 4 cells of a contingency table, the 3
+  Brier-type statistics): one launch -- `cat` = {'thresholds', **extra} -- for up to `block` thresholds; more are cut into blocks --
+  thresholds are independent of one another --, one launch each, joined on the host group by group: the result is
+  (ngroup * K,) + out_dims whatever the number of launches.  ONE launch is handed on as it is: nothing is joined, so the result may
+  still be pending (deferred read-back, chunk records)."""
+  thr = np.asarray(thr, np.float64)
+  nthr = int(thr.size)
+  if nthr <= block:
+    return launch(dict(extra, thresholds=thr))
+  # (group, k of the block) + out_dims; the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from
+  groups = lambda a: a.reshape((ngroup, a.shape[0] // ngroup) + a.shape[1:])
+  return _reduce_in_blocks([dict(extra, thresholds=np.ascontiguousarray(thr[k0:k0 + block])) for k0 in range(0, nthr, block)], launch,
+                           lambda parts: np.concatenate([groups(a) for a in parts], axis=1).reshape(
+                               (ngroup * nthr,) + parts[0].shape[1:]))
+
+
 def _group_known(p, t, kind: str, pred=lambda key: True) -> bool:
   """A group of kind `kind` of these very objects exists (`pred`: of the rest of its key): an earlier statistic has checked
   their frames."""
@@ -236,7 +254,8 @@ def _group_known(p, t, kind: str, pred=lambda key: True) -> bool:
 
 
 class FusedGroup:
-  """All fused statistics over one (predictions, targets[, climatology]) triple."""
+  """All fused statistics over one (predictions, targets[, climatology]) triple.  What differs between kinds -- input 2, how `reduce`
+  runs, where per-point values come from -- is a row of `_LAZY_KINDS` below."""
 
   def __init__(self, kind: str, p: xr.DataArray, t: xr.DataArray, ens=None, cat=None):
     self.kind = kind
@@ -244,15 +263,15 @@ class FusedGroup:
     self.ens = ens  # {'member_dim', 'M'}; kind 'enrg': + {'fair' (None: no spread statistic has said yet), 'norm_dims', 'norm_sizes'};
     # kind 'vgrm': + {'fair': False, 'norm_dims' (the score's one dim), 'norm_sizes', 'power'}; kinds 'ens2', 'wass': + {'N'}
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
-    # 'quantile_dim'} (engine.reduce_statistics), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
+    # 'quantile_dim'} (engine._ivl_operands), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
     # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
     # per size, or None), 'thresholds' (float64 ndarray, or None: binary inputs), 'threshold_dim', 'coord'} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic);
     # kind 'erpsf': {'bin_dim', 'nthr', 'side_dim', 'right_inclusive', 'host'} (ens_rps_field_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
-    if kind in ('enrg', 'vgrm'):  # a point is one index of the frame without the member dim and the dims the norm / the pairs run over
-      drop += tuple(ens['norm_dims'])
+    if ens:  # a point is one index of the frame without the member dim and the dims the norm / the pairs run over ('enrg', 'vgrm')
+      drop += tuple(ens.get('norm_dims', ()))
     self.dims, self.sizes, self.coords = _stat_frame([p, t], drop_dims=drop)
     self.cache: dict = {}
 
@@ -273,7 +292,7 @@ class FusedGroup:
 
   @property
   def mask(self) -> xr.DataArray | None:
-    if self.kind == 'seeps' and self.cat.get('mask_da') is not None:
+    if self.cat and self.cat.get('mask_da') is not None:  # ('seeps': the places whose dry fraction is in range)
       return self.cat['mask_da']
     if 'mask' in self.coords:
       cd, cv = self.coords['mask']
@@ -283,44 +302,32 @@ class FusedGroup:
 
   # -- execution ---------------------------------------------------------------------------------
   def inputs_and_func(self):
-    if self.kind in ('ens', 'cat', 'ens2', 'cont', 'erps', 'enrg', 'vgrm', 'wass', 'epc', 'fss', 'brier'):
-      return [self.p, self.t], 0
-    if self.kind == 'ivl':
-      return ([self.p, self.t, self.clim.source] if self.clim is not None else [self.p, self.t]), 0
-    if self.kind in ('seeps', 'erpsf'):
-      return [self.p, self.t, self.clim.source], 0
-    if self.clim is not None:
-      return [self.p, self.t, self.clim.source], _hip.DET6
-    return [self.p, self.t], _hip.DET3
+    third = _LAZY_KINDS[self.kind].third
+    inputs = [self.p, self.t]
+    if third == 'required' or (third == 'optional' and self.clim is not None):
+      inputs.append(self.clim.source)
+    if self.kind != 'det':
+      return inputs, 0
+    return inputs, (_hip.DET6 if self.clim is not None else _hip.DET3)  # (the climatology brings the anomaly lanes with it)
+
+  def _ens(self, ens_params):
+    """The group's `ens` under the settings a statistic of kind 'ens' brings along (algo, fair, skipna)."""
+    return dict(self.ens, **ens_params) if ens_params else self.ens
 
   def reduce(self, reduce_dims, w_da, bin_dims, *, use_mask: bool, skipna: bool, ens_params=None, extra_reduce=()):
+    how = _LAZY_KINDS[self.kind].reduce
     inputs, func = self.inputs_and_func()
     mask = self.mask if use_mask else None
     reduce_dims = tuple(reduce_dims) + tuple(extra_reduce)
-    if self.kind in ('det', 'ens'):
-      ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
+    if how in (_GATHER, _GATHER_IN_PLACE):
       return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
-                                 skipna=skipna, clim=self.clim, ens=ens)
-    if self.kind in ('ivl', 'erpsf'):  # 'ivl': one launch for every lane asked for so far; the climatology / the threshold field
-      # gathered in place like ACC's climatology
-      return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
-                                 skipna=skipna, clim=self.clim, ens=self.ens, cat=self.cat)
-    if self.kind == 'seeps':  # the wet thresholds gathered in place like ACC's climatology; the score table addresses their places
-      return _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
-                                 skipna=skipna, clim=self.clim, ens=None, cat=self.cat, may_align=False)
-    if self.kind == 'fss':
+                                 skipna=skipna, clim=self.clim, ens=self._ens(ens_params), cat=self.cat, may_align=how == _GATHER)
+    if how == _PER_SIZE:
       return self._reduce_fss(inputs, reduce_dims, w_da, bin_dims, use_mask, skipna)
-    # 'ens2', 'wass', 'erps', 'enrg', 'vgrm': one launch (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm'
-    # group are its own); 'cat', 'cont', 'epc', 'brier': one per block
+    # (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm' group are its own)
     launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
                                                   skipna=skipna, ens=self.ens, cat=cat)
-    if self.kind == 'cat':
-      return self._reduce_cat(launch, mask, skipna)
-    if self.kind == 'epc':
-      return self._reduce_epc(launch)
-    if self.kind == 'brier':
-      return self._reduce_brier(launch)
-    return self._reduce_cont(launch) if self.kind == 'cont' else launch(self.cat)
+    return launch(self.cat) if how == _PLAIN else how(self, launch, mask, skipna)
 
   def _reduce_cat(self, launch, mask, skipna):
     """Indicator statistics: one launch where the categories fit its LDS columns (cat_lanes_per_launch), else -- thresholds
@@ -336,34 +343,6 @@ class FusedGroup:
     if ncat <= block:
       return launch(cat)
     return _reduce_in_blocks(self._cat_blocks(block), launch, lambda parts: np.concatenate(parts, axis=0))
-
-  def _reduce_cont(self, launch):
-    """Thresholded contingency tables: one launch for up to _hip.CONT_MAX_THRESHOLDS thresholds; more are cut into blocks --
-    thresholds are independent of one another --, one launch each, joined on the host cell by cell: the result is
-    (4 * K,) + out_dims with lane cell * K + k whatever the number of launches."""
-    thr = np.asarray(self.cat['thresholds'], np.float64)
-    nthr, block = int(thr.size), _hip.CONT_MAX_THRESHOLDS
-    if nthr <= block:
-      return launch({'thresholds': thr})
-    # (cell, k of the block) + out_dims; the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from
-    cells = lambda a: a.reshape((_hip.CONT_CELLS, a.shape[0] // _hip.CONT_CELLS) + a.shape[1:])
-    return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block])} for k0 in range(0, nthr, block)], launch,
-                             lambda parts: np.concatenate([cells(a) for a in parts], axis=1).reshape(
-                                 (_hip.CONT_CELLS * nthr,) + parts[0].shape[1:]))
-
-  def _reduce_brier(self, launch):
-    """Error, AbsoluteError and SquaredError of event probabilities: one launch for up to _hip.BRIER_MAX_THRESHOLDS thresholds; more
-    are cut into blocks -- thresholds are independent of one another --, one launch each, joined on the host statistic by
-    statistic: the result is (3 * K,) + out_dims with lane stat * K + k whatever the number of launches."""
-    thr = np.asarray(self.cat['thresholds'], np.float64)
-    nthr, block, ns, denom = int(thr.size), _hip.BRIER_MAX_THRESHOLDS, _hip.BRIER_STATS, int(self.cat['denom'])
-    if nthr <= block:
-      return launch({'thresholds': thr, 'denom': denom})
-    # (stat, k of the block) + out_dims; the sizes are spelled out: an out dim of length 0 leaves nothing to infer them from
-    stats = lambda a: a.reshape((ns, a.shape[0] // ns) + a.shape[1:])
-    return _reduce_in_blocks([{'thresholds': np.ascontiguousarray(thr[k0:k0 + block]), 'denom': denom} for k0 in range(0, nthr, block)],
-                             launch, lambda parts: np.concatenate([stats(a) for a in parts], axis=1).reshape(
-                                 (ns * nthr,) + parts[0].shape[1:]))
 
   def _reduce_fss(self, inputs, reduce_dims, w_da, bin_dims, use_mask, skipna):
     """The three terms of the fractions skill score: one launch per neighbourhood size (wbx_fss_partial; the shared count lane of a
@@ -446,60 +425,19 @@ class FusedGroup:
     return memo[block]
 
   def materialise(self, lane: int, ens_params=None) -> np.ndarray:
-    if self.kind == 'erps':
-      # the per-point values are the host route's, bit for bit (the indicator arrays of the two ContinuousToCDF transforms and
-      # labelled-array arithmetic on them): whoever reads them sees what it saw before the fused reduction existed
-      from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
-      cat = self.cat
-      stat = multivariate.EnsembleRankedProbabilityScore(
-          cat['p_values'], cat['t_values'], cat['bin_dim'], '', ensemble_dim=self.ens['member_dim'], skipna_ensemble=False,
-          fair=self.ens['fair'], enforce_monotonicity=False, right_inclusive=cat['right_inclusive'])
-      out = stat.host_per_variable(self.p, self.t)
-      return out.transpose(*self.dims).data
-    if self.kind == 'enrg':
-      # the per-point values are the host route's, bit for bit, in whatever array type it gives (a tensor for torch payloads)
-      from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
-      ens = self.ens
-      if lane == ENERGY_LANE['EnergyScoreSkill']:
-        stat = multivariate.EnergyScoreSkill(dim=list(ens['norm_dims']), ensemble_dim=ens['member_dim'])
-      else:
-        stat = multivariate.EnergyScoreSpread(dim=list(ens['norm_dims']), ensemble_dim=ens['member_dim'], fair=ens['fair'] is not False)
-      out = stat.host_per_variable(self.p, self.t)
-      return out.transpose(*self.dims).data
-    if self.kind in ('seeps', 'erpsf'):  # the host route's per-point values (categorical.SEEPS._one; EnsembleRankedProbabilityScore
-      # .host_per_variable), in whatever array type it gives
-      out = self.cat['host'](self.p, self.t)
-      return out.transpose(*self.dims).data
-    if self.kind == 'vgrm':  # the host route's per-point values, as for 'enrg'
-      from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
-      ens = self.ens
-      stat = multivariate.VariogramScore(dim=ens['norm_dims'][0], ensemble_dim=ens['member_dim'], p=ens['power'])
-      out = stat.host_per_variable(self.p, self.t)
-      return out.transpose(*self.dims).data
-    if self.kind in ('ens2', 'wass'):  # stage 1 with every dim kept IS the per-point statistic
+    row = _LAZY_KINDS[self.kind]
+    if row.host is not None:
+      # the per-point values are the host route's, bit for bit, in whatever array type it gives (a tensor for torch payloads):
+      # whoever reads them sees what it saw before the fused reduction existed
+      return row.host(self, lane)(self.p, self.t).transpose(*self.dims).data
+    if row.points is not None:  # stage 1 with every dim kept IS the per-point statistic ('ivl': `lane` among the lanes launched)
       with engine.synchronous_results():
         values, _, out_dims = self.reduce((), None, (), use_mask=False, skipna=False)
       arr = np.asarray(values, np.float64)[lane]
-      arr = np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims]))
-      if self.kind == 'wass':  # a float64 tensor where a payload is one, on its device: the array type the host route gives
-        for da in (self.p, self.t):
-          if xr._is_torch(da.data):  # pylint: disable=protected-access
-            import torch  # pylint: disable=g-import-not-at-top
-            return torch.as_tensor(arr, device=da.data.device)
-      return arr
-    if self.kind == 'ivl':  # stage 1 with every dim kept, as for 'wass'; `lane`: the value lane among those launched
-      with engine.synchronous_results():
-        values, _, out_dims = self.reduce((), None, (), use_mask=False, skipna=False)
-      arr = np.asarray(values, np.float64)[lane] != 0
-      arr = np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims]))
-      if xr._is_torch(self.p.data):  # pylint: disable=protected-access  (a Boolean tensor on the payload's device, as the host route gives)
-        import torch  # pylint: disable=g-import-not-at-top
-        return torch.as_tensor(arr, device=self.p.data.device)
-      return arr
+      return row.points(self, np.ascontiguousarray(np.transpose(arr, [out_dims.index(d) for d in self.dims])))
     inputs, func = self.inputs_and_func()
-    ens = dict(self.ens, **(ens_params or {})) if self.kind == 'ens' else None
-    gather, inputs = _gather_spec(self.clim, inputs, self.dims)
-    return engine.materialise(self.kind, inputs, self.dims, self.sizes, lane, func=func, gather=gather, ens=ens)
+    gather, inputs = _gather_spec(self.clim, inputs, self.dims, self.kind)
+    return engine.materialise(self.kind, inputs, self.dims, self.sizes, lane, func=func, gather=gather, ens=self._ens(ens_params))
 
 
 def gather_from_ref(clim: ClimatologyRef, dtype_code: int) -> planner.GatherSpec:
@@ -519,17 +457,15 @@ def gather_from_ref(clim: ClimatologyRef, dtype_code: int) -> planner.GatherSpec
 
 
 def _gather_dtype(kind, inputs) -> int:
-  """The dtype input 2 goes to the device in: the inputs' common one; kind 'erpsf': the threshold field's own."""
-  if kind == 'erpsf':
+  """The dtype input 2 goes to the device in: the inputs' common one, or its own (engine._KINDS: 'erpsf', the threshold field)."""
+  if engine._KINDS[kind].own_dtype2:  # pylint: disable=protected-access
     return engine.own_dtype(inputs[2])
   return engine._common_dtype([i.data for i in inputs])  # pylint: disable=protected-access
 
 
-def _gather_spec(clim: ClimatologyRef | None, inputs, dims, kind=None):
+def _gather_spec(clim: ClimatologyRef | None, inputs, dims, kind):
   """Element-offset gather table for the climatology input, from its device layout."""
-  if clim is None:
-    return None, inputs
-  if kind == 'erpsf' and not clim.positions:  # a threshold field without a time dim: nothing to gather
+  if clim is None or not clim.positions:  # (no positions: a threshold field without a time dim, nothing to gather)
     return None, inputs
   return gather_from_ref(clim, _gather_dtype(kind, inputs)), inputs
 
@@ -570,7 +506,7 @@ def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, 
   rec = replay.active() if clim is not None else None
   if rec is not None:  # a chunk that is being recorded: what its gather plans have to be rebuilt from for the next chunk
     rec.gather_context = {'source': clim.origin[0] if clim.origin is not None else clim.source, 'p': inputs[0], 'over_dims': tuple(clim.over_dims),
-                          'dtype_code': _gather_dtype(kind, inputs), 'regather': _regather_bins if kind == 'erpsf' else _regather}
+                          'dtype_code': _gather_dtype(kind, inputs), 'regather': _LAZY_KINDS[kind].regather}
   try:
     return engine.reduce_statistics(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, func=func, mask=mask,
                                     skipna=skipna, gather=gather, ens=ens, cat=cat)
@@ -585,6 +521,70 @@ def _reduce_with_gather(kind, inputs, dims, sizes, reduce_dims, w_da, bin_dims, 
   finally:
     if rec is not None:
       rec.gather_context = None
+
+
+def _like_payload(arr, *das):
+  """`arr` as a tensor on the device of the first of `das` whose payload is one -- the array type the host route gives --, else as
+  it is."""
+  for da in das:
+    if xr._is_torch(da.data):  # pylint: disable=protected-access
+      import torch  # pylint: disable=g-import-not-at-top
+      return torch.as_tensor(arr, device=da.data.device)
+  return arr
+
+
+def _rebuilt(build):
+  """host(group, lane) of a row below: the host route of the `multivariate` statistic that `build(multivariate, group, lane)` makes
+  from what the group holds."""
+  def host(g, lane):
+    from weatherbenchx_amd.metrics import multivariate  # pylint: disable=g-import-not-at-top
+    return build(multivariate, g, lane).host_per_variable
+  return host
+
+
+# What FusedGroup does per kind, beside engine._KINDS (the same keys).  Rows are looked up by `group.kind` when needed: nothing
+# callable is kept on a group or a statistic, which are pickled.
+#   third:    input 2, the source of `group.clim` (a climatology, the wet thresholds, a threshold field): None, 'optional' ('det': it
+#             also chooses DET6 over DET3) or 'required'
+#   reduce:   _GATHER: one launch through _reduce_with_gather, input 2 gathered in place like ACC's climatology ('ivl': one launch for
+#             every lane asked for so far) and aligned first where the selection runs along the innermost dim;  _GATHER_IN_PLACE:
+#             the same, never aligned ('seeps': its score table is addressed by the climatology's own places);  _PER_SIZE: one
+#             launch per neighbourhood size under that size's mask (FusedGroup._reduce_fss);  _PLAIN: one launch;  or
+#             blocks(group, launch, mask, skipna): one launch(cat) per block of what a launch holds, joined on the host
+#   host:     host(group, lane) -> (p, t) -> the host route's per-point values, what `.values` of a statistic gives;  else
+#   points:   points(group, arr) -> the per-point values from `arr`, lane `lane` of stage 1 with every dim kept, float64 over the
+#             group's dims, in the array type the host route gives;  neither: engine.materialise
+#   regather: of a recorded chunk's gather context (replay.ChunkRecord), how input 2 is gathered for the next chunk
+_GATHER, _GATHER_IN_PLACE, _PER_SIZE, _PLAIN = 'gather', 'gather in place', 'per size', 'plain'
+_LazyKind = collections.namedtuple('_LazyKind', 'third reduce host points regather', defaults=(None, _PLAIN, None, None, _regather))
+_host_of_cat = lambda g, lane: g.cat['host']  # (categorical.SEEPS._one; EnsembleRankedProbabilityScore.host_per_variable)
+_LAZY_KINDS = {
+    'det': _LazyKind('optional', _GATHER),
+    'ens': _LazyKind(None, _GATHER),
+    'ens2': _LazyKind(points=lambda g, arr: arr),
+    'cat': _LazyKind(reduce=FusedGroup._reduce_cat),  # pylint: disable=protected-access
+    'cont': _LazyKind(reduce=lambda g, launch, mask, skipna: _reduce_threshold_blocks(
+        launch, g.cat['thresholds'], _hip.CONT_CELLS, _hip.CONT_MAX_THRESHOLDS)),
+    'erps': _LazyKind(host=_rebuilt(lambda mv, g, lane: mv.EnsembleRankedProbabilityScore(  # (the indicator arrays of the two
+        # ContinuousToCDF transforms and labelled-array arithmetic on them)
+        g.cat['p_values'], g.cat['t_values'], g.cat['bin_dim'], '', ensemble_dim=g.ens['member_dim'], skipna_ensemble=False,
+        fair=g.ens['fair'], enforce_monotonicity=False, right_inclusive=g.cat['right_inclusive']))),
+    'erpsf': _LazyKind('required', _GATHER, host=_host_of_cat, regather=_regather_bins),
+    'epc': _LazyKind(reduce=lambda g, launch, mask, skipna: g._reduce_epc(launch)),  # pylint: disable=protected-access
+    'brier': _LazyKind(reduce=lambda g, launch, mask, skipna: _reduce_threshold_blocks(
+        launch, g.cat['thresholds'], _hip.BRIER_STATS, _hip.BRIER_MAX_THRESHOLDS, denom=int(g.cat['denom']))),
+    'enrg': _LazyKind(host=_rebuilt(lambda mv, g, lane:
+                                    mv.EnergyScoreSkill(dim=list(g.ens['norm_dims']), ensemble_dim=g.ens['member_dim'])
+                                    if lane == ENERGY_LANE['EnergyScoreSkill'] else
+                                    mv.EnergyScoreSpread(dim=list(g.ens['norm_dims']), ensemble_dim=g.ens['member_dim'],
+                                                         fair=g.ens['fair'] is not False))),
+    'vgrm': _LazyKind(host=_rebuilt(lambda mv, g, lane: mv.VariogramScore(dim=g.ens['norm_dims'][0], ensemble_dim=g.ens['member_dim'],
+                                                                          p=g.ens['power']))),
+    'wass': _LazyKind(points=lambda g, arr: _like_payload(arr, g.p, g.t)),
+    'ivl': _LazyKind('optional', _GATHER, points=lambda g, arr: _like_payload(arr != 0, g.p)),  # (Boolean statistics)
+    'seeps': _LazyKind('required', _GATHER_IN_PLACE, host=_host_of_cat),
+    'fss': _LazyKind(reduce=_PER_SIZE),
+}
 
 
 def _group_for(kind: str, p: xr.DataArray, t: xr.DataArray, ens=None, clim_key=None, cat=None) -> FusedGroup:
