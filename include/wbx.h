@@ -658,6 +658,43 @@ int wbx_ens_brier_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WB
                           const double* thresholds /* DEVICE float64[nthr] */, const void* p, const void* t, const uint8_t* mask,
                           double* partial_out);
 
+/* ---- stage 1: errors of ensemble quantiles (joined ABI 13) ------------------------------------------------------------
+ * Error, AbsoluteError and SquaredError (deterministic.py:91-123) of the quantiles of an ensemble against the target, behind
+ * EnsembleQuantiles('predictions', quantiles) (wrappers.py:151-211): MAE of the ensemble median, Bias / MSE / RMSE of deciles, in one
+ * pass that sorts a point's members once: no float64 [nq][frame] quantile array is formed.  p has a member axis of length M and
+ * element stride `member_stride`, which is not part of key / depth / x.  `bounds` is a HOST array of nq wbx_ivl_bound, read during
+ * the call; `c_off` is ignored.
+ * Per point, with target t:
+ *   Members are sorted in the input type (exact).  A flag gathered while they are loaded marks a NaN member (the sort's min / max
+ *   drop a NaN: it cannot come from propagation).  Quantile j with the bound (k_j, g_j) -- the host forms h = q (M - 1), k = floor(h),
+ *   g = h - k in float64 -- is NumPy's `linear` method in NumPy's order of operations and NumPy's types: with A = x_(k),
+ *   B = x_(min(k + 1, M - 1)) and d = B - A formed IN THE INPUT TYPE (np.quantile subtracts the neighbours before the float64 weight
+ *   joins: for float32 members d is rounded to float32; wbx_ens_interval_partial widens first and differs there), it is, in float64,
+ *       A + d g         where g < 0.5,
+ *       B - d (1 - g)   otherwise,
+ *   every product and sum rounded on its own, with no shortcut for g == 0 (inf * 0 gives the NaN NumPy gives), and NaN where the flag
+ *   is set: np.quantile(members, q) of the members as they are, bit for bit.  Then
+ *       e_j = q_j - (double)t
+ *       lane ERR * nq + j : e_j      lane ABS * nq + j : |e_j|      lane SQ * nq + j : e_j * e_j
+ *   the product rounded before it is added: there is no fused multiply-add between forming a value and accumulating it.
+ * Lane order is part of the ABI: WBX_QERR_STATS * nq value lanes, stat * nq + j, stat in (ERR, ABS, SQ) = (0, 1, 2).
+ * Sums are float64.  A lane adds its points in the order they come, lanes, waves and blocks are added in fixed orders and nothing is
+ * added atomically: a partial is a function of the inputs and the plan only.
+ * NaN handling is the deterministic family's: without flags a NaN value poisons its lane of the partial; under WBX_FLAG_MASKED a point
+ * adds exactly 0 where the mask is 0 (and poisons where it is not); under WBX_FLAG_SKIPNA a NaN value is counted out of its own lane.
+ * Count lanes follow the library's convention (none / one shared under a mask alone / one per value lane under skipna: +-inf members
+ * can make one quantile NaN and not another).  partial_out[nkey][nchunk][lanes_total][nj] as for wbx_det_partial:
+ * wbx_s1_partial_len with lanes = 3 * nq; wbx_contract, wbx_contract_bits, the accumulators and the chunk records take it unchanged.
+ * Refused (WBX_ERR_INVALID, output untouched): M outside 1..WBX_IVL_MAX_MEMBERS, nq outside 1..WBX_QERR_MAX_QUANTILES, a bound with k
+ * outside 0..M-1 or g outside [0, 1), NULL `bounds`, an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask,
+ * plane_rows != 0 or x_weights, NULL p or t on a non-empty plan.  vec = 4 is accepted and ignored; a block runs block_threads threads
+ * up to what its LDS holds (128 for float32, 64 for float64).  nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial. */
+#define WBX_QERR_STATS 3           /* ERR, ABS, SQ */
+#define WBX_QERR_MAX_QUANTILES 16  /* per launch */
+int wbx_ens_quantile_error_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* WBX_F32 | WBX_F64 */, int M,
+                                   int64_t member_stride, int nq, const wbx_ivl_bound* bounds /* HOST, nq entries; c_off ignored */,
+                                   const void* p, const void* t, const uint8_t* mask, double* partial_out);
+
 /* ---- stage 1: SEEPS from a per-place score table (joined ABI 13) ----------------------------------------------------
  * The stable equitable error in probability space (categorical.py:104-304) of a prediction p against a target t: both are put
  * into a category against the dry threshold and the point's climatological wet threshold, and the pair of categories picks one of
@@ -1022,7 +1059,8 @@ typedef enum wbx_fn {
   WBX_FN_CONTINGENCY_PARTIAL = 20, WBX_FN_ENS_RPS_PARTIAL = 21, WBX_FN_ENS_ENERGY_PARTIAL = 22,
   WBX_FN_ENS_VARIOGRAM_PARTIAL = 23, WBX_FN_ENS_WASSERSTEIN_PARTIAL = 24, WBX_FN_ENS_INTERVAL_PARTIAL = 25,
   WBX_FN_ENS_PROB_CONTINGENCY_PARTIAL = 26, WBX_FN_SEEPS_PARTIAL = 27, WBX_FN_FSS_PARTIAL = 28,
-  WBX_FN_ENS_BRIER_PARTIAL = 29, WBX_FN_FSS_THRESHOLD_PARTIAL = 30, WBX_FN_ENS_RPS_FIELD_PARTIAL = 31
+  WBX_FN_ENS_BRIER_PARTIAL = 29, WBX_FN_FSS_THRESHOLD_PARTIAL = 30, WBX_FN_ENS_RPS_FIELD_PARTIAL = 31,
+  WBX_FN_ENS_QUANTILE_ERROR_PARTIAL = 32
 } wbx_fn;
 #define WBX_CALL_MAX_ARGS 20
 typedef struct wbx_call {

@@ -42,6 +42,8 @@ EPC_MAX_MEMBERS = 256  # (WBX_EPC_MAX_MEMBERS)
 BRIER_STATS = 3  # wbx_ens_brier_partial: value lane stat * nthr + k, stat in (ERR, ABS, SQ) (WBX_BRIER_STATS)
 BRIER_MAX_THRESHOLDS = 16  # per launch (WBX_BRIER_MAX_THRESHOLDS)
 BRIER_MAX_MEMBERS = 256  # (WBX_BRIER_MAX_MEMBERS)
+QERR_STATS = 3  # wbx_ens_quantile_error_partial: value lane stat * nq + j, stat in (ERR, ABS, SQ) (WBX_QERR_STATS)
+QERR_MAX_QUANTILES = 16  # per launch (WBX_QERR_MAX_QUANTILES)
 SEEPS_LANES = 1  # wbx_seeps_partial (WBX_SEEPS_LANES)
 SEEPS_CELLS = 9  # cells of its score table: 3 * (category of p) + (category of t) (WBX_SEEPS_CELLS)
 FSS_LANES = 3  # wbx_fss_partial: (Pf - Tf)^2, Pf^2, Tf^2 (WBX_FSS_LANES)
@@ -71,7 +73,7 @@ EXPORTED_SYMBOLS = (
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
     'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial', 'wbx_ens_brier_partial',
-    'wbx_fss_threshold_partial', 'wbx_ens_rps_field_partial',
+    'wbx_fss_threshold_partial', 'wbx_ens_rps_field_partial', 'wbx_ens_quantile_error_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -83,7 +85,7 @@ FN_IDS = {'wbx_det_partial': 1, 'wbx_ens_partial': 2, 'wbx_ens2_partial': 3, 'wb
           'wbx_ens_variogram_partial': 23, 'wbx_ens_wasserstein_partial': 24, 'wbx_ens_interval_partial': 25,
           'wbx_ens_prob_contingency_partial': 26, 'wbx_seeps_partial': 27, 'wbx_fss_partial': 28,
           'wbx_ens_brier_partial': 29, 'wbx_fss_threshold_partial': 30,
-          'wbx_ens_rps_field_partial': 31}
+          'wbx_ens_rps_field_partial': 31, 'wbx_ens_quantile_error_partial': 32}
 CALL_MAX_ARGS = 20
 # pure queries: they touch neither a stream nor memory, a record simply leaves them out
 QUERY_FNS = frozenset({'wbx_s1_partial_len', 'wbx_binned_atoms_size', 'wbx_ens_binned_atoms_size', 'wbx_last_error',
@@ -282,6 +284,7 @@ def load_library():
         'wbx_ens_prob_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, i32, vp, vp, vp, vp, vp],
         'wbx_ens_brier_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, i32, vp, vp, vp, vp, vp],
         'wbx_ens_interval_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlLaneStruct), vp, vp, vp, vp, vp],
+        'wbx_ens_quantile_error_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, C.POINTER(IvlBoundStruct), vp, vp, vp, vp],
         'wbx_seeps_partial': [vp, C.POINTER(S1PlanStruct), i32, C.c_double, vp, vp, vp, vp, i64, vp, vp],
         'wbx_fss_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, vp, vp, vp, vp],
         'wbx_fss_threshold_partial': [vp, C.POINTER(FssPlanStruct), i32, i32, i32, vp, vp, vp, vp, vp],

@@ -33,14 +33,6 @@ struct IvlArgs {
   int32_t np;            // M padded to a generated network size
 };
 
-// The smallest generated network that holds m members (tests/interval_cases.py restates it).
-static inline int ivl_padded(int m) {
-  const int sizes[] = {4, 8, 16, 32, 50, 51, 64};
-  for (int s : sizes)
-    if (m <= s) return s;
-  return 0;
-}
-
 // NumPy's linear quantile of the parked sorted column at the bound b; `nan`: the point has a NaN member.
 template <typename T>
 __device__ __forceinline__ double ivl_quantile(const T* col, int cs, int M, const wbx_ivl_bound& b, bool nan) {

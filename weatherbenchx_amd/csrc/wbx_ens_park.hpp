@@ -1,6 +1,6 @@
 // One point per lane: a point's ensemble members loaded into registers, padded to a generated network size, sorted there and parked
 // as a column in LDS, where order statistics are read at wave-uniform rows.  Shared by the kernels that need a whole sorted
-// ensemble per point at run-time ranks (wbx_ens_wasserstein.hip, wbx_ens_interval.hip).
+// ensemble per point at run-time ranks (wbx_ens_wasserstein.hip, wbx_ens_interval.hip, wbx_ens_quantile.hip).
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -75,6 +75,14 @@ __device__ __forceinline__ void wass_park(const T* pp, int64_t stride, int M, T*
   wass_load_sort<T, NS>(pp, stride, M, x, nan);
 #pragma unroll
   for (int k = 0; k < NS; ++k) col[k * cs] = x[k];
+}
+
+// The smallest generated network that holds m members (tests/interval_cases.py and tests/quantile_error_cases.py restate it).
+static inline int ivl_padded(int m) {
+  const int sizes[] = {4, 8, 16, 32, 50, 51, 64};
+  for (int s : sizes)
+    if (m <= s) return s;
+  return 0;
 }
 
 }  // namespace wbx

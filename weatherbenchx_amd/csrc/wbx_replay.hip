@@ -76,6 +76,7 @@ extern "C" int wbx_chunk_replay(wbx_call* calls, int32_t ncalls, const wbx_reloc
       WBX_REPLAY_CASE(WBX_FN_ENS_BRIER_PARTIAL, wbx_ens_brier_partial)
       WBX_REPLAY_CASE(WBX_FN_FSS_THRESHOLD_PARTIAL, wbx_fss_threshold_partial)
       WBX_REPLAY_CASE(WBX_FN_ENS_RPS_FIELD_PARTIAL, wbx_ens_rps_field_partial)
+      WBX_REPLAY_CASE(WBX_FN_ENS_QUANTILE_ERROR_PARTIAL, wbx_ens_quantile_error_partial)
       WBX_REPLAY_CASE(WBX_FN_CONTRACT, wbx_contract)
       WBX_REPLAY_CASE(WBX_FN_CONTRACT_BITS, wbx_contract_bits)
       WBX_REPLAY_CASE(WBX_FN_DET_BINNED, wbx_det_binned)

@@ -500,6 +500,7 @@ ens_wasserstein_available = lambda ctx: _entry_available(ctx, 'wbx_ens_wasserste
 ens_interval_available = lambda ctx: _entry_available(ctx, 'wbx_ens_interval_partial')
 ens_prob_available = lambda ctx: _entry_available(ctx, 'wbx_ens_prob_contingency_partial')
 brier_available = lambda ctx: _entry_available(ctx, 'wbx_ens_brier_partial')
+ens_quantile_available = lambda ctx: _entry_available(ctx, 'wbx_ens_quantile_error_partial')
 seeps_available = lambda ctx: _entry_available(ctx, 'wbx_seeps_partial')
 fss_thresholds_available = lambda ctx: _entry_available(ctx, 'wbx_fss_threshold_partial')
 fss_available = lambda ctx: _entry_available(ctx, 'wbx_fss_partial')
@@ -786,6 +787,8 @@ RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
 RpsFieldArgs = collections.namedtuple('RpsFieldArgs', 'thr_dtype nthr thr_stride t_off right')  # (the field itself is input 2)
 EpcArgs = collections.namedtuple('EpcArgs', 'nthr thr nslot slots')
 BrierEnsArgs = collections.namedtuple('BrierEnsArgs', 'm mstride denom')
+QerrEnsArgs = collections.namedtuple('QerrEnsArgs', 'm mstride')
+QerrArgs = collections.namedtuple('QerrArgs', 'nthr thr bounds')  # thr: always None (no table); bounds: a HOST array of _hip.IvlBoundStruct
 EnergyArgs = collections.namedtuple('EnergyArgs', 'm mstride norm_len p_norm_stride t_norm_stride')
 VariogramArgs = collections.namedtuple('VariogramArgs', 'm mstride run_len p_run_stride t_run_stride power')
 IvlEnsArgs = collections.namedtuple('IvlEnsArgs', 'm mstride lanes')
@@ -865,7 +868,10 @@ def _epc_operands(ctx, devs, func, ens, cat, mdim):
 def _brier_operands(ctx, devs, func, ens, cat, mdim):
   """Error, AbsoluteError and SquaredError of event probabilities: `ens` = {'member_dim', 'M', 'fair': False} or None (a
   deterministic pair: M = 1), `cat` = {'thresholds': float64 ndarray of at most _hip.BRIER_MAX_THRESHOLDS, 'denom': M or M + 1, 1
-  without a member dim}; value lane stat * K + k, stat in (Error, AbsoluteError, SquaredError)."""
+  without a member dim}; value lane stat * K + k, stat in (Error, AbsoluteError, SquaredError).  `cat` with 'quantiles' set: the
+  row's second arm, _qerr_operands."""
+  if cat.get('quantiles'):
+    return _qerr_operands(ctx, devs, func, ens, cat, mdim)
   thr = np.asarray(cat['thresholds'], np.float64).reshape(-1)
   nthr, m, denom = int(thr.size), int(ens['M']) if ens else 1, int(cat['denom'])
   if not 1 <= nthr <= _hip.BRIER_MAX_THRESHOLDS:
@@ -877,6 +883,25 @@ def _brier_operands(ctx, devs, func, ens, cat, mdim):
   if mdim is None:  # one "member": the entry ignores the stride
     return _hip.BRIER_STATS * nthr, BrierEnsArgs(1, 0, 1), ContArgs(nthr, _const_table(ctx, thr))
   return _hip.BRIER_STATS * nthr, BrierEnsArgs(m, devs[0].layout.stride(mdim), denom), ContArgs(nthr, _const_table(ctx, thr))
+
+
+def _qerr_operands(ctx, devs, func, ens, cat, mdim):
+  """The second arm of 'brier': Error, AbsoluteError and SquaredError of ensemble quantiles.  `ens` = {'member_dim', 'M', 'fair':
+  False}, `cat` = {'quantiles': True, 'thresholds': float64 ndarray of at most _hip.QERR_MAX_QUANTILES quantile LEVELS in [0, 1]};
+  value lane stat * Q + j.  The bounds (k, g) are formed here, in float64, as for the interval statistics (ivl_bound)."""
+  levels = np.asarray(cat['thresholds'], np.float64).reshape(-1)
+  nq, m = int(levels.size), int(ens['M']) if ens else 0
+  if not 1 <= nq <= _hip.QERR_MAX_QUANTILES:
+    raise ValueError(f'one quantile error launch takes 1..{_hip.QERR_MAX_QUANTILES} quantiles (got {nq})')
+  if mdim is None or not 1 <= m <= _hip.IVL_MAX_MEMBERS:
+    raise ValueError(f'one quantile error launch takes 1..{_hip.IVL_MAX_MEMBERS} members (got {m})')
+  bounds = (_hip.IvlBoundStruct * nq)()
+  for bound, q in zip(bounds, levels):
+    k, g = ivl_bound(q, m) if q == q else (-1, 0.0)
+    if not (0 <= k < m and 0.0 <= g < 1.0):
+      raise ValueError(f'quantile level {float(q)!r} is outside [0, 1]')
+    bound.k, bound.g, bound.c_off = k, g, 0
+  return _hip.QERR_STATS * nq, QerrEnsArgs(m, devs[0].layout.stride(mdim)), QerrArgs(nq, None, bounds)
 
 
 def norm_run(layout, dims, sizes):
@@ -1076,7 +1101,9 @@ _KINDS = {
                  ('wbx_ens_prob_contingency_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), int(cat.nslot),
                                                        _table_ptr(cat.slots), d[0], d[1], d[3], out))),
     'brier': _Kind(_brier_operands, ('thr',),
-                   lambda d, out, dt, func, ens, cat:
+                   lambda d, out, dt, func, ens, cat:  # no threshold table: the errors of ensemble quantiles (host bounds instead)
+                   ('wbx_ens_quantile_error_partial', (dt, *map(int, ens), int(cat.nthr), cat.bounds, d[0], d[1], d[3], out))
+                   if cat.thr is None else
                    ('wbx_ens_brier_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.thr), d[0], d[1], d[3], out))),
     'enrg': _Kind(_enrg_operands, (),
                   lambda d, out, dt, func, ens, cat: ('wbx_ens_energy_partial', (dt, *map(int, ens), d[0], d[1], d[3], out))),

@@ -91,6 +91,10 @@ FUSED_FSS_THRESHOLDS = os.environ.get('WBX_FUSED_FSS_THRESHOLDS', '1') != '0'
 # and reduce them as before wbx_ens_brier_partial existed (A/B timing, tests).
 FUSED_BRIER = os.environ.get('WBX_FUSED_BRIER', '1') != '0'
 BRIER_STAT = {'Error': 0, 'AbsoluteError': 1, 'SquaredError': 2}  # lane blocks (wbx.h)
+# False (WBX_FUSED_ENS_QUANTILES=0): Error, AbsoluteError and SquaredError behind EnsembleQuantiles('predictions') build the float64
+# [Q, frame] quantile array on the host (np.quantile / torch.quantile) and reduce the statistic of it as before
+# wbx_ens_quantile_error_partial existed (A/B timing, tests).
+FUSED_ENS_QUANTILES = os.environ.get('WBX_FUSED_ENS_QUANTILES', '1') != '0'
 CONT_CELL = {'TruePositives': 0, 'FalsePositives': 1, 'FalseNegatives': 2, 'TrueNegatives': 3}  # lane blocks (wbx.h)
 
 _frame_memo: list = [None]  # (weakref p, weakref t, mutations, frame without drop_dims): the last (p, t) frame that was computed
@@ -265,7 +269,7 @@ class FusedGroup:
     self.cat = cat  # indicator statistics: {'func', 'ncat', 'thresholds', 'member_dim', 'M'}; kind 'ivl': {'lanes', 'params',
     # 'quantile_dim'} (engine._ivl_operands), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
     # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
-    # per size, or None), 'thresholds' (float64 ndarray, or None: binary inputs), 'threshold_dim', 'coord'} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic);
+    # per size, or None), 'thresholds' (float64 ndarray, or None: binary inputs), 'threshold_dim', 'coord'} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic) or {'quantiles': True, 'thresholds': the levels, 'values', 'coord', 'threshold_dim'} (quantile_error_statistic);
     # kind 'erpsf': {'bin_dim', 'nthr', 'side_dim', 'right_inclusive', 'host'} (ens_rps_field_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
@@ -571,8 +575,11 @@ _LAZY_KINDS = {
         fair=g.ens['fair'], enforce_monotonicity=False, right_inclusive=g.cat['right_inclusive']))),
     'erpsf': _LazyKind('required', _GATHER, host=_host_of_cat, regather=_regather_bins),
     'epc': _LazyKind(reduce=lambda g, launch, mask, skipna: g._reduce_epc(launch)),  # pylint: disable=protected-access
-    'brier': _LazyKind(reduce=lambda g, launch, mask, skipna: _reduce_threshold_blocks(
-        launch, g.cat['thresholds'], _hip.BRIER_STATS, _hip.BRIER_MAX_THRESHOLDS, denom=int(g.cat['denom']))),
+    'brier': _LazyKind(reduce=lambda g, launch, mask, skipna:  # (quantile levels, not event thresholds: the row's second arm)
+                       _reduce_threshold_blocks(launch, g.cat['thresholds'], _hip.QERR_STATS, _hip.QERR_MAX_QUANTILES, quantiles=True)
+                       if g.cat.get('quantiles') else
+                       _reduce_threshold_blocks(launch, g.cat['thresholds'], _hip.BRIER_STATS, _hip.BRIER_MAX_THRESHOLDS,
+                                                denom=int(g.cat['denom']))),
     'enrg': _LazyKind(host=_rebuilt(lambda mv, g, lane:
                                     mv.EnergyScoreSkill(dim=list(g.ens['norm_dims']), ensemble_dim=g.ens['member_dim'])
                                     if lane == ENERGY_LANE['EnergyScoreSkill'] else
@@ -984,6 +991,72 @@ def brier_statistic(stat: str, p, t, ensemble_dim, threshold_dim: str, threshold
   cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim, 'denom': int(denom)}
   grp = _group_for('brier', p, t, ens=ens, clim_key=ckey, cat=cat)
   return LazyBrier(grp, BRIER_STAT[stat], name=p.name)
+
+
+class LazyQuantileError(LazyBrier):
+  """Error, AbsoluteError or SquaredError of (the quantiles of the members of `p`) against `t` along a new LEADING `quantile_dim`:
+  what these statistics are behind EnsembleQuantiles('predictions', quantiles).  The three statistics of one (p, t) pair, list of
+  levels, member dim and quantile dim share a FusedGroup of kind 'brier' whose `cat` has 'quantiles' set, so the Aggregator gets all of
+  them from one launch (wbx_ens_quantile_error_partial), through the lane-block route of LazyBrier.  Reading `.data` runs the
+  transform and the statistic as labelled-array arithmetic on the host and needs no device."""
+
+  def __init__(self, group: FusedGroup, stat: int, name=None):
+    super().__init__(group, stat, name=name)
+    self._dims = (self._threshold_dim,) + tuple(group.dims)  # (the host route's order: transform_fn puts the new dim first)
+    self._coords[self._threshold_dim] = ((self._threshold_dim,), np.asarray(group.cat['coord'], np.float64))
+
+  @property
+  def result_dims(self) -> tuple:
+    return self._dims
+
+  @staticmethod
+  def launchable() -> bool:
+    try:
+      return FUSED_ENS_QUANTILES and engine.ens_quantile_available(_hip.default_context())
+    except _hip.WbxUnavailableError:
+      return False
+
+  @property
+  def data(self):
+    if self._data is None:
+      from weatherbenchx_amd.metrics import wrappers  # pylint: disable=g-import-not-at-top
+      grp, cat = self._group, self._group.cat
+      pq = wrappers.EnsembleQuantiles('predictions', list(cat['values']), self._threshold_dim, grp.ens['member_dim']).transform_fn(grp.p)
+      d = pq - grp.t
+      out = (d, abs(d), d ** 2)[self._cell]
+      self._data = out.transpose(*self._dims).data
+    return self._data
+
+  @property
+  def shape(self):
+    return self.lane_shape + tuple(self._group.sizes[d] for d in self._group.dims)
+
+  @property
+  def dtype(self):  # NumPy's quantiles are float64 whatever the members are; torch.quantile stays in the input dtype
+    p = self._group.p
+    return np.dtype(str(p.dtype)) if xr._is_torch(p.data) else np.dtype(np.float64)  # pylint: disable=protected-access
+
+
+def quantile_error_statistic(stat: str, p, t, ensemble_dim: str, quantile_dim: str, quantiles) -> xr.DataArray:
+  """`stat` ('Error', 'AbsoluteError', 'SquaredError') of the `quantiles` (levels in [0, 1]) of the members of `p` against `t` as a
+  LazyQuantileError with the host route's dims, (quantile_dim,) + frame, and its float64 quantile coordinate.  The (p, t) objects, the
+  levels' bytes, the member dim and the quantile dim key the group, so the three statistics of a pair meet in one group."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if ensemble_dim not in p.dims or ensemble_dim in t.dims:
+    raise ValueError(f'{ensemble_dim!r} must be a dim of the predictions and not of the targets')
+  if quantile_dim in p.dims or quantile_dim in t.dims or quantile_dim == ensemble_dim:
+    raise ValueError(f'{quantile_dim!r} is already a dimension of the inputs')
+  values = [float(q) for q in quantiles]
+  levels = np.asarray(values, np.float64).reshape(-1)
+  if not levels.size or not np.all((levels >= 0.0) & (levels <= 1.0)):
+    raise ValueError('Quantiles must be in the range [0, 1]')
+  ckey = ('qerr', quantile_dim, levels.tobytes())
+  if not _group_known(p, t, 'brier', lambda k: k[3] == ensemble_dim and k[4] == ckey):
+    p, t = _aligned(p, t)
+  ens = {'member_dim': ensemble_dim, 'M': p.sizes[ensemble_dim], 'fair': False}
+  cat = {'quantiles': True, 'thresholds': levels, 'values': values, 'coord': levels, 'threshold_dim': quantile_dim}
+  grp = _group_for('brier', p, t, ens=ens, clim_key=ckey, cat=cat)
+  return LazyQuantileError(grp, BRIER_STAT[stat], name=p.name)
 
 
 class LazyFSS(xr.LazyPickleMixin, xr.DataArray):

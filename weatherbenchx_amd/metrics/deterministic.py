@@ -138,11 +138,59 @@ def _fused_brier(stat, transforms, predictions, targets):
   return {name: lazy.brier_statistic(type(stat).__name__, p, t, e, dim, values, denom) for name, (p, t, denom) in pairs.items()}
 
 
+def _fused_quantiles(stat, transform, predictions, targets):
+  """`stat` (Error, AbsoluteError or SquaredError) behind exactly EnsembleQuantiles('predictions', quantiles, quantile_dim, e,
+  skipna=False) as lazy statistics on the members (one fused launch for the three statistics of a variable,
+  lazy.quantile_error_statistic), or None: the caller then transforms and computes as usual.
+  None for any other transform or `which`, skipna=True, an ensemble dim that the predictions lack or the targets have, a `quantile`
+  dim or the quantile dim already on an input or equal to the ensemble dim, target dims other than the frame (the prediction dims
+  without the ensemble dim), dtypes other than float32 / float64 or two different ones, fewer than 1 or more than
+  _hip.IVL_MAX_MEMBERS members, no quantile, one outside [0, 1], NaN or not a number, a `mask` coordinate along the member dim, a
+  subclass of the three statistics, no device, no library, no entry point, the switch off.  The gate never raises: where the host
+  route would, it does."""
+  from weatherbenchx_amd import engine  # pylint: disable=g-import-not-at-top
+  from weatherbenchx_amd.metrics import wrappers  # pylint: disable=g-import-not-at-top
+  if not lazy.FUSED_ENS_QUANTILES or type(stat) not in _BRIER_STATS:  # pylint: disable=unidiomatic-typecheck
+    return None
+  if type(transform) is not wrappers.EnsembleQuantiles or transform.which != 'predictions' or transform._skipna:  # pylint: disable=unidiomatic-typecheck,protected-access
+    return None
+  e, dim = transform._ensemble_dim, transform._quantile_dim  # pylint: disable=protected-access
+  try:
+    levels = [float(q) for q in transform._quantiles]  # pylint: disable=protected-access
+  except (TypeError, ValueError):
+    return None
+  if not levels or not all(0.0 <= q <= 1.0 for q in levels) or not isinstance(e, str) or not isinstance(dim, str) or e == dim:
+    return None
+  pairs = {}
+  for name in predictions.keys():
+    if name not in targets.keys():
+      continue
+    p, t = base._named(predictions[name], name), base._named(targets[name], name)  # pylint: disable=protected-access
+    if e not in p.dims or e in t.dims or not 1 <= p.sizes[e] <= _hip.IVL_MAX_MEMBERS:
+      return None
+    if {dim, 'quantile'} & (set(p.dims) | set(t.dims)) or set(t.dims) != set(p.dims) - {e}:
+      return None
+    if str(p.dtype) not in ('float32', 'float64') or str(t.dtype) != str(p.dtype):
+      return None
+    if 'mask' in p.coords and e in p.coords['mask'].dims:
+      return None
+    pairs[name] = (p, t)
+  try:
+    ctx = _hip.default_context()
+  except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on
+    return None
+  if not engine.ens_quantile_available(ctx):
+    return None
+  return {name: lazy.quantile_error_statistic(type(stat).__name__, p, t, e, dim, levels) for name, (p, t) in pairs.items()}
+
+
 class _BrierGates:
-  """What wrappers.WrappedStatistic asks a statistic that may know a fused form of itself behind its transforms (_fused_brier)."""
+  """What wrappers.WrappedStatistic asks a statistic that may know a fused form of itself behind its transforms (_fused_brier,
+  _fused_quantiles)."""
 
   def compute_with_transform(self, transform, predictions, targets):
-    return _fused_brier(self, (transform,), predictions, targets)
+    fused = _fused_brier(self, (transform,), predictions, targets)
+    return fused if fused is not None else _fused_quantiles(self, transform, predictions, targets)
 
   def compute_with_chain(self, transforms, predictions, targets):
     return _fused_brier(self, tuple(transforms), predictions, targets) if len(transforms) == 2 else None
