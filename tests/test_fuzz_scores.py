@@ -152,6 +152,14 @@ def draw_case(family, seed):
   if rng.random() < 0.5:
     bd = [str(d) for d in rng.permutation(c.stat_dims)[:int(rng.integers(1, min(2, len(c.stat_dims)) + 1))]]
     c.bins = (bd, rng.random([int(rng.choice([2, 7]))] + [sizes[d] for d in bd]) > 0.4)
+  draw_mode(c, rng, pv, tv, [d for d in c.tdims if d != E and d not in c.norm])  # never along the member dim or a norm dim
+  c.pv, c.tv = pv, tv
+  return c
+
+
+def draw_mode(c, rng, pv, tv, own):
+  """Draws c.mode and c.mask and puts the mode's NaNs into the payloads: one NaN each ('nan_plain'), a sprinkle ('skipna'), a mask
+  over some of the targets' dims `own` with a NaN target under a masked-out point ('masked')."""
   c.mode = str(rng.choice(MODES))
   c.mask = None
   spot = lambda a: tuple(int(rng.integers(0, s)) for s in a.shape)
@@ -162,19 +170,16 @@ def draw_case(family, seed):
     tv[rng.random(tv.shape) < 0.02] = np.nan
     pv[rng.random(pv.shape) < 0.01] = np.nan
   elif c.mode == 'masked':
-    own = [d for d in c.tdims if d != E and d not in c.norm]  # never along the member dim or a norm dim
     if not own:
       c.mode = 'plain'  # (targets of norm dims only: nothing to put a mask on)
     else:
       mdims = [d for d in own if rng.random() < 0.6] or own[:1]
-      mask = rng.random([sizes[d] for d in mdims]) > 0.25
+      mask = rng.random([c.sizes[d] for d in mdims]) > 0.25
       c.mask = (tuple(mdims), mask)
       hidden = np.argwhere(~mask)
       if hidden.size:  # a NaN target under a masked-out point: it must leave no trace
         at = dict(zip(mdims, hidden[int(rng.integers(0, len(hidden)))]))
         tv[tuple(int(at[d]) if d in at else int(rng.integers(0, tv.shape[i])) for i, d in enumerate(c.tdims))] = np.nan
-  c.pv, c.tv = pv, tv
-  return c
 
 
 # ---- the gates, restated from their docstrings ----------------------------------------------------------------------------------------
@@ -302,31 +307,40 @@ def check_against_the_restatement(c, state, pv, tv, emulated, fused=True):
   # weights on dims the statistic does not have (the norm dims) are 1 (VectorWeighting)
   ow = [(v, (d,)) for d, v in c.weights if d in c.stat_dims]
   ob = [('bin0', c.bins[1], ('bin0',) + tuple(c.bins[0]))] if c.bins else []
-  n = int(np.prod([c.sizes[d] for d in c.reduce]))
   worst = 0.0
   for name, (stat, b_f, b_64, masked, host_mag) in expected_points(c, pv, tv, fused).items():
-    tag = (c.family, c.seed, name)
     mkw = dict(mask=c.mask[1], mask_dims=c.mask[0]) if (c.mode == 'masked' and masked) else {}
     agg = lambda a, **kw: O.aggregate(a, c.stat_dims, c.reduce, weights=ow, bin_masks=ob, **mkw, **kw)
-    sws, sw, out_dims = agg(stat, skipna=c.mode == 'skipna')
-    finite = np.isfinite(stat)
-    own = agg(np.where(finite, b_f + 2.0 * b_64, 0.0))[0]
-    mag = agg(np.where(finite, np.abs(stat), 0.0))[0]
-    bound = 1e-12 * agg(np.where(finite, host_mag, 0.0))[0] if emulated else own + (n + 4) * 2.0 ** -52 * mag
     got_s, got_w = state.sum_weighted_statistics[name].get('v'), state.sum_weights[name].get('v')
-    assert got_s is not None and set(got_s.dims) == set(out_dims), (tag, got_s if got_s is None else got_s.dims, out_dims)
-    got = np.asarray(got_s.transpose(*out_dims).values, np.float64)
-    np.testing.assert_array_equal(np.isnan(got), np.isnan(sws), err_msg=f'{tag}: NaN cells')
-    inf = np.isinf(sws)
-    np.testing.assert_array_equal(got[inf], sws[inf], err_msg=f'{tag}: infinite cells')
-    fin = np.isfinite(sws)
-    err = np.abs(got[fin] - sws[fin])
-    with np.errstate(all='ignore'):
-      ratio = float(np.where(err > 0, err / bound[fin], 0.0).max()) if err.size else 0.0
-    assert (err <= bound[fin]).all(), (tag, 'worst error / bound', ratio, 'largest error', float(err.max()))
-    worst = max(worst, ratio)
-    np.testing.assert_allclose(np.asarray(got_w.transpose(*out_dims).values), sw, rtol=1e-12, atol=0, err_msg=f'{tag}: weights')
+    worst = max(worst, check_cells((c.family, c.seed, name), got_s, got_w, agg, stat, b_f, b_64, host_mag, c.reduce, c.sizes,
+                                   c.mode == 'skipna', emulated))
   return worst
+
+
+def check_cells(tag, got_s, got_w, agg, stat, b_f, b_64, host_mag, reduce, sizes, skipna, emulated, host_own=None):
+  """One statistic's sums and weights against its per-point values `stat` aggregated by `agg` (O.aggregate under the case's weights,
+  bins and mask; the dims of `stat` may include lane dims: ordinary dims there) -> the worst error / bound.  `host_own`: a per-point
+  bound that the emulated half grants on top of its 1e-12 (arithmetic that the host route does in float32 whatever the payload)."""
+  n = int(np.prod([sizes[d] for d in reduce]))
+  sws, sw, out_dims = agg(stat, skipna=skipna)
+  finite = np.isfinite(stat)
+  own = agg(np.where(finite, b_f + 2.0 * b_64, 0.0))[0]
+  mag = agg(np.where(finite, np.abs(stat), 0.0))[0]
+  bound = 1e-12 * agg(np.where(finite, host_mag, 0.0))[0] if emulated else own + (n + 4) * 2.0 ** -52 * mag
+  if emulated and host_own is not None:
+    bound = bound + agg(np.where(finite, host_own, 0.0))[0]
+  assert got_s is not None and set(got_s.dims) == set(out_dims), (tag, got_s if got_s is None else got_s.dims, out_dims)
+  got = np.asarray(got_s.transpose(*out_dims).values, np.float64)
+  np.testing.assert_array_equal(np.isnan(got), np.isnan(sws), err_msg=f'{tag}: NaN cells')
+  inf = np.isinf(sws)
+  np.testing.assert_array_equal(got[inf], sws[inf], err_msg=f'{tag}: infinite cells')
+  fin = np.isfinite(sws)
+  err = np.abs(got[fin] - sws[fin])
+  with np.errstate(all='ignore'):
+    ratio = float(np.where(err > 0, err / bound[fin], 0.0).max()) if err.size else 0.0
+  assert (err <= bound[fin]).all(), (tag, 'worst error / bound', ratio, 'largest error', float(err.max()))
+  np.testing.assert_allclose(np.asarray(got_w.transpose(*out_dims).values), sw, rtol=1e-12, atol=0, err_msg=f'{tag}: weights')
+  return ratio
 
 
 def run_host_arrays(c, backend, monkeypatch):
@@ -383,15 +397,16 @@ def test_most_seeds_are_eligible(family):
 
 
 # ---- 3. device-resident payloads with the strides they come with ----------------------------------------------------------------------------
-def _physical_orders(c, seed):
+def _physical_orders(c, seed, families=FAMILIES, base=69000):
   """-> (the order the predictions are stored in, the targets', whether the views start one element into their allocations, the
-  frame dim along which they are every other element of an allocation twice as long, or None)."""
-  rng = np.random.default_rng(69000 + seed)
+  frame dim along which they are every other element of an allocation twice as long, or None).  `families`: the families the
+  caller rotates over with the seed; `base`: its own stream of random numbers."""
+  rng = np.random.default_rng(base + seed)
   p_stored = [str(d) for d in rng.permutation(c.pdims)]
   t_stored = [str(d) for d in rng.permutation(c.tdims)]
-  turn = seed // len(FAMILIES)  # (the family rotates with the seed: a third and a quarter of every family's seeds)
+  turn = seed // len(families)  # (the family rotates with the seed: a third and a quarter of every family's seeds)
   offset = turn % 3 == 0
-  sliced = str(rng.choice([d for d in c.pdims if d != E])) if turn % 4 == seed % len(FAMILIES) else None
+  sliced = str(rng.choice([d for d in c.pdims if d != E])) if turn % 4 == seed % len(families) % 4 else None
   return p_stored, t_stored, offset, sliced
 
 
