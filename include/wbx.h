@@ -440,6 +440,34 @@ int wbx_ens_rps_field_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /
                               int64_t t_off, int right_inclusive, const void* p, const void* t, const void* c, const uint8_t* mask,
                               double* partial_out);
 
+/* ---- stage 1: thresholded 2x2 contingency tables at threshold FIELDS (joined ABI 13) ---------------------------
+ * wbx_contingency_partial with the thresholds read at the point: TruePositives .. TrueNegatives behind
+ * ContinuousToBinary('both', field, dim) whose thresholds are a DataArray / Dataset (wrappers.py:50-88), such as "exceeds the
+ * local climatological 95th percentile", without the [nthr][frame] indicator arrays.  `c` is input 2 of the plan (key_off[2],
+ * depth_off[2], xstride[2], the gather tables; zero strides where it does not vary), exactly as for wbx_ens_rps_field_partial
+ * and wbx_cat_exceed_field.  With A the address of a point in c, in elements of `thr_dtype`:
+ *     thr_k = c[A + (thr_first + k) * thr_stride],   k in 0..nthr-1         (thr_first: the first threshold of this launch, so
+ *                                                                            that blocks of a longer threshold axis share one c)
+ *     P_k = p > thr_k,  O_k = t > thr_k    (strict; both sides read the same threshold, which is loaded once)
+ * The cells, the lanes (value lane cell * nthr + k), the count lanes, NaN p or t (poisons / masked out / counted out), the
+ * partial (integers < 2^32 in fp64 or NaN, a function of the inputs and the plan only, no atomics) and the layout of
+ * partial_out are those of wbx_contingency_partial, word for word.
+ * A comparison with a NaN threshold is false: the point counts towards TN when p and t are not NaN, which is
+ * (x > NaN).where(~isnan(x)).  This is UNLIKE wbx_ens_rps_field_partial, where a NaN threshold makes the point a NaN point.
+ * Comparisons decide as NumPy's promoted comparison does: equal types compare as they are; float32 thresholds against float64
+ * data widen exactly; float64 thresholds against float32 data are rounded per point to float32 toward -inf (x > v <=> x > rd(v)
+ * for every non-NaN float32 x; NaN stays NaN, a value beyond the float32 range decides right) and compared in float32.
+ * Refused (WBX_ERR_INVALID, output untouched): everything wbx_contingency_partial refuses (nthr outside
+ * 1..WBX_CONT_MAX_THRESHOLDS, an unknown dtype, flags beyond MASKED | SKIPNA, WBX_FLAG_MASKED with a NULL mask, plane_rows != 0
+ * or x_weights, depth_chunk * nx >= 2^32), an unknown thr_dtype, thr_stride == 0 with nthr > 1, thr_first < 0, and a NULL c
+ * unless the extent is empty.  vec = 4 is honoured where x is summed: p, t and -- where xstride[2] == 1 -- the field's row are
+ * read with 16-byte loads of element alignment, so thr_stride needs no alignment of its own.
+ * nkey == 0 touches nothing; ndepth == 0 or nx == 0 zero the partial, whatever c is.
+ * The entry is not among the wbx_fn a chunk record may hold (wbx_chunk_replay): a chunk that launches it is evaluated call by call. */
+int wbx_contingency_field_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, int dtype /* p, t: WBX_F32 | WBX_F64 */,
+                                  int thr_dtype /* c: WBX_F32 | WBX_F64 */, int nthr, int64_t thr_stride, int64_t thr_first,
+                                  const void* p, const void* t, const void* c, const uint8_t* mask, double* partial_out);
+
 /* ---- stage 1: energy score of an ensemble, both terms (joined ABI 13) -------------------------------------------
  * EnergyScoreSkill and EnergyScoreSpread (probabilistic.py:480-551) of an ensemble of predictions against a target, in one pass
  * over p and t instead of one whole-array pass per cyclic member offset.  p has a member axis of length M and element stride

@@ -21,7 +21,7 @@ DET_LANES = {DET3: 3, DET6: 6, PASS1: 1}
 DET_INPUTS = {DET3: 2, DET6: 3, PASS1: 1}
 CAT_EXCEED, CAT_RANK = 0, 1
 CONT_CELLS = 4  # wbx_contingency_partial: value lane cell * nthr + k, cell in (TP, FP, FN, TN)
-CONT_MAX_THRESHOLDS = 16  # per launch (WBX_CONT_MAX_THRESHOLDS)
+CONT_MAX_THRESHOLDS = 16  # per launch (WBX_CONT_MAX_THRESHOLDS); wbx_contingency_field_partial has both as well
 ERPS_MAX_THRESHOLDS = 16  # wbx_ens_rps_partial and wbx_ens_rps_field_partial, per launch (WBX_ERPS_MAX_THRESHOLDS)
 ERPS_MAX_MEMBERS = 256  # (WBX_ERPS_MAX_MEMBERS: a point's integer numerator fits an int32)
 ENRG_LANES = 2  # wbx_ens_energy_partial: skill, spread (WBX_ENRG_LANES)
@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = (
     'wbx_contingency_partial', 'wbx_ens_rps_partial', 'wbx_ens_energy_partial',
     'wbx_ens_variogram_partial', 'wbx_ens_wasserstein_partial', 'wbx_ens_interval_partial',
     'wbx_ens_prob_contingency_partial', 'wbx_seeps_partial', 'wbx_fss_partial', 'wbx_ens_brier_partial',
-    'wbx_fss_threshold_partial', 'wbx_ens_rps_field_partial', 'wbx_ens_quantile_error_partial',
+    'wbx_fss_threshold_partial', 'wbx_ens_rps_field_partial', 'wbx_ens_quantile_error_partial', 'wbx_contingency_field_partial',
 )
 
 # wbx_fn (include/wbx.h): the entry points a chunk record may hold
@@ -276,6 +276,7 @@ def load_library():
         'wbx_cat_exceed_field': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i64, vp, vp, vp, i64, vp, vp],
         'wbx_cat_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i32, i64, vp, vp, vp, vp, vp],
         'wbx_contingency_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, vp, vp, vp, vp, vp],
+        'wbx_contingency_field_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i64, i64, vp, vp, vp, vp, vp],
         'wbx_ens_rps_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i32, vp, vp, i32, vp, vp, vp, vp],
         'wbx_ens_rps_field_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i32, i64, i32, i64, i64, i32, vp, vp, vp, vp, vp],
         'wbx_ens_energy_partial': [vp, C.POINTER(S1PlanStruct), i32, i32, i64, i64, i64, i64, vp, vp, vp, vp],

@@ -19,64 +19,9 @@
 #include <type_traits>
 
 #include "wbx_cont_threshold.hpp"
-#include "wbx_s1.hpp"
+#include "wbx_contingency.hpp"
 
 namespace wbx {
-
-constexpr int CONT_MAX_WAVES = 4;
-
-// V consecutive x of one row (unit x stride: one 16-byte load -- four mask bytes: one dword --, element aligned type as in
-// wbx_det.hip) or V strided elements; x stride 0 broadcasts.  p / t are streamed, mask bytes stay cached.
-template <typename T, int V>
-__device__ __forceinline__ void cont_load(const void* base, int64_t off, int64_t x, int64_t xs, T (&v)[V]) {
-  const T* p = reinterpret_cast<const T*>(base) + off;
-  if constexpr (V == 4) {
-    if (xs == 1) {
-      if constexpr (sizeof(T) == 1) {
-        const uint32_t q = *reinterpret_cast<const uint32_t*>(p + x);
-        v[0] = (T)(q & 0xffu);
-        v[1] = (T)((q >> 8) & 0xffu);
-        v[2] = (T)((q >> 16) & 0xffu);
-        v[3] = (T)(q >> 24);
-      } else {
-        typedef T v4_t __attribute__((ext_vector_type(4), aligned(sizeof(T))));
-        const v4_t q = __builtin_nontemporal_load(reinterpret_cast<const v4_t*>(p + x));
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-      }
-    } else {  // xs == 0 (check_plan: vec = 4 has unit / zero x strides)
-      const T s = p[0];
-      v[0] = v[1] = v[2] = v[3] = s;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if constexpr (sizeof(T) > 1)
-        v[k] = ld_stream(p + (x + k) * xs);
-      else
-        v[k] = p[(x + k) * xs];
-    }
-  }
-}
-
-// The four cells of threshold k (and the count lanes) from the integer counts, into lanes o[lane * nj].
-__device__ __forceinline__ void cont_write(double* o, int64_t nj, int nthr, int k, uint32_t flags, uint32_t tp, uint32_t np,
-                                           uint32_t no, uint32_t ngood, uint32_t nvalid) {
-  const bool skipna = flags & WBX_FLAG_SKIPNA;
-  const bool poisoned = !skipna && ngood != nvalid;  // a NaN under a valid point
-  double v[WBX_CONT_CELLS] = {(double)tp, (double)(np - tp), (double)(no - tp), (double)(ngood - np - no + tp)};
-#pragma unroll
-  for (int c = 0; c < WBX_CONT_CELLS; ++c) o[(int64_t)(c * nthr + k) * nj] = poisoned ? (double)NAN : v[c];
-  const int nl = WBX_CONT_CELLS * nthr;
-  if (skipna) {
-#pragma unroll
-    for (int c = 0; c < WBX_CONT_CELLS; ++c) o[(int64_t)(nl + c * nthr + k) * nj] = (double)ngood;
-  } else if ((flags & WBX_FLAG_MASKED) && k == 0) {
-    o[(int64_t)nl * nj] = (double)nvalid;
-  }
-}
 
 // x summed.  grid = nkey * nchunk, block = plan->block_threads; rows are dealt to the waves as in s1_xr_kernel.
 template <typename T, int V, int NT, bool MASKED>
@@ -143,6 +88,7 @@ __global__ void __launch_bounds__(256) cont_xr_kernel(S1Args a, const double* th
     }
   }
 
+  // (wbx_contingency_field.hip has these lines as contf_block_write: as a shared function they change this unit's registers)
   __shared__ uint32_t red[CONT_MAX_WAVES][3 * WBX_CONT_MAX_THRESHOLDS + 2];
   if (lane == 0) {
 #pragma unroll
@@ -238,15 +184,7 @@ extern "C" int wbx_contingency_partial(wbx_ctx* ctx, const wbx_s1_plan* plan, in
   using namespace wbx;
   const S1Names names = {"wbx_contingency_partial: ", "partial_out", "p/t"};
   if (int rc = s1_begin(names.who, ctx, plan)) return rc;
-  WBX_REQUIRE(nthr >= 1 && nthr <= WBX_CONT_MAX_THRESHOLDS, "wbx_contingency_partial: 1..%d thresholds per launch (got %d)",
-              WBX_CONT_MAX_THRESHOLDS, nthr);
-  WBX_REQUIRE(dtype == WBX_F32 || dtype == WBX_F64, "wbx_contingency_partial: unknown dtype %d", dtype);
-  WBX_REQUIRE(!(plan->flags & ~(WBX_FLAG_MASKED | WBX_FLAG_SKIPNA)), "wbx_contingency_partial: flags other than MASKED | SKIPNA (0x%x)",
-              plan->flags);
-  WBX_REQUIRE(plan->plane_rows == 0 && plan->x_weights == nullptr, "wbx_contingency_partial: no plane mode, no folded x weights");
-  // uint32 counters: a partial meets at most depth_chunk * nx points
-  WBX_REQUIRE((double)plan->depth_chunk * (double)(plan->nx > 0 ? plan->nx : 1) < 4294967296.0,
-              "wbx_contingency_partial: 2^32 or more points per partial (depth_chunk * nx)");
+  if (int rc = cont_requirements(names.who, plan, dtype, nthr)) return rc;
   S1Args a;
   if (int rc = s1_operands(names, ctx, plan, 2, p, t, mask, partial_out, a)) return rc;
   const int nacc = (int)partial_lanes(plan->flags, WBX_CONT_CELLS * nthr);

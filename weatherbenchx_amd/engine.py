@@ -387,7 +387,7 @@ def _planned_inner(ctx, kind, dims, sizes, layouts, reduce_dims, wdep, gather, f
                                  allow_vec4=(_KINDS[kind].vec4 and x_weights is None and force_x is None), force_x_dim=force_x,
                                  fold_x=False if x_weights is None else
                                  (True if kind == 'det' else ('point64' if one_wave else 'point')))
-    if kind == 'cont' and plan.plane_rows > 0:  # 16-byte loads yes, plane mode no: wbx_contingency_partial walks rows
+    if kind == 'cont' and plan.plane_rows > 0:  # 16-byte loads yes, plane mode no: the contingency kernels walk rows
       plan = planner.build_s1_plan(dims, sizes, layouts, reduce_dims, wdep_dims=wdep, gather=gather, flags=flags,
                                    allow_vec4=False, force_x_dim=force_x)
     if x_weights is not None and plan.plane_rows > 0:
@@ -492,6 +492,7 @@ def _entry_available(ctx, *symbols) -> bool:
 
 # the gates of the fused statistics (metrics/*.py and lazy.py look them up through the module at call time; tests patch them)
 contingency_available = lambda ctx: _entry_available(ctx, 'wbx_contingency_partial')
+contingency_field_available = lambda ctx: _entry_available(ctx, 'wbx_contingency_field_partial')
 ens_rps_available = lambda ctx: _entry_available(ctx, 'wbx_ens_rps_partial')
 ens_rps_field_available = lambda ctx: _entry_available(ctx, 'wbx_ens_rps_field_partial')
 ens_energy_available = lambda ctx: _entry_available(ctx, 'wbx_ens_energy_partial')
@@ -783,6 +784,7 @@ RpsEnsArgs = collections.namedtuple('RpsEnsArgs', 'm mstride')
 Ens2Args = collections.namedtuple('Ens2Args', 'm mstride n_t tstride')
 CatArgs = collections.namedtuple('CatArgs', 'func ncat m mstride thr cstride')  # thr: a table; None with cstride: a field (input 2)
 ContArgs = collections.namedtuple('ContArgs', 'nthr thr')
+ContFieldArgs = collections.namedtuple('ContFieldArgs', 'thr_dtype nthr thr_stride thr_first')  # (no table: the field itself is input 2)
 RpsArgs = collections.namedtuple('RpsArgs', 'nthr p_thr t_thr right')
 RpsFieldArgs = collections.namedtuple('RpsFieldArgs', 'thr_dtype nthr thr_stride t_off right')  # (the field itself is input 2)
 EpcArgs = collections.namedtuple('EpcArgs', 'nthr thr nslot slots')
@@ -810,11 +812,36 @@ def _cat_operands(ctx, devs, func, ens, cat, mdim):
 
 def _cont_operands(ctx, devs, func, ens, cat, mdim):
   """Thresholded contingency tables: `cat` = {'thresholds': float64 ndarray of at most _hip.CONT_MAX_THRESHOLDS}; value lane
-  cell * nthr + k, cell in (TP, FP, FN, TN)."""
+  cell * nthr + k, cell in (TP, FP, FN, TN).  `cat` with 'threshold_dim' set: the row's second arm, _contf_operands."""
+  if cat.get('threshold_dim') is not None:
+    return _contf_operands(ctx, devs, func, ens, cat, mdim)
   nthr = int(np.asarray(cat['thresholds']).size)
   if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
     raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
   return _hip.CONT_CELLS * nthr, None, ContArgs(nthr, _const_table(ctx, cat['thresholds']))
+
+
+def _contf_operands(ctx, devs, func, ens, cat, mdim):
+  """Kind 'cont' at a threshold field: inputs (p, t, the field: input 2, behind `gather` where a selection runs along a time
+  dim), `cat` = {'threshold_dim': the field's dim the thresholds lie along, 'nthr': thresholds of this launch, at most
+  _hip.CONT_MAX_THRESHOLDS, 'thr_first': the position of the first of them along 'threshold_dim' (blocks of a longer axis share one
+  field)}.  What the entry is told beside them comes from the field as it lies on the device: 'thr_stride', the element stride of
+  'threshold_dim', and 'thr_dtype', the field's own dtype -- it is not widened to the inputs' (the kernel compares as NumPy
+  promotes).  Value lane cell * nthr + k, cell in (TP, FP, FN, TN)."""
+  if devs[2] is None:
+    raise ValueError('contingency tables at a threshold field need the field (input 2)')
+  nthr, first = int(cat['nthr']), int(cat.get('thr_first', 0))
+  if not 1 <= nthr <= _hip.CONT_MAX_THRESHOLDS:
+    raise ValueError(f'one contingency launch takes 1..{_hip.CONT_MAX_THRESHOLDS} thresholds (got {nthr})')
+  size = int(cat.get('size', first + nthr))
+  if first < 0 or first + nthr > size:
+    raise ValueError(f"thresholds {first}..{first + nthr - 1} are not all on the field's threshold dim of length {size}")
+  thr_stride = devs[2].layout.stride(cat['threshold_dim'])
+  if thr_stride == 0:  # a dim of length 1 is never stepped along; a longer one that is broadcast (an expanded tensor) has no stride to step by
+    if size > 1:
+      raise ValueError(f"the field's threshold dim {cat['threshold_dim']!r} of length {size} has stride 0 (a broadcast view): make it contiguous")
+    thr_stride = 1
+  return _hip.CONT_CELLS * nthr, None, ContFieldArgs(devs[2].dtype_code, nthr, thr_stride, first)
 
 
 def _check_ranges(what, count_ok, counts, ens, max_members):
@@ -1085,8 +1112,12 @@ _KINDS = {
                  ('wbx_cat_partial', (int(cat.func), dt, int(cat.ncat), int(cat.m), int(cat.mstride), d[0], d[1], _table_ptr(cat.thr),
                                       d[3], out))),
     'cont': _Kind(_cont_operands, ('thr',),
-                  lambda d, out, dt, func, ens, cat:
-                  ('wbx_contingency_partial', (dt, int(cat.nthr), d[0], d[1], _table_ptr(cat.thr), d[3], out)), vec4=True),
+                  lambda d, out, dt, func, ens, cat:  # no threshold table: a threshold FIELD, input 2, kept like the one of 'erpsf'
+                  ('wbx_contingency_field_partial', (dt, int(cat.thr_dtype), int(cat.nthr), int(cat.thr_stride), int(cat.thr_first),
+                                                     d[0], d[1], d[2], d[3], out))
+                  if isinstance(cat, ContFieldArgs) else
+                  ('wbx_contingency_partial', (dt, int(cat.nthr), d[0], d[1], _table_ptr(cat.thr), d[3], out)),
+                  vec4=True, own_dtype2=True, keep2=True),
     'erps': _Kind(_erps_operands, ('p_thr', 't_thr'),
                   lambda d, out, dt, func, ens, cat:
                   ('wbx_ens_rps_partial', (dt, *map(int, ens), int(cat.nthr), _table_ptr(cat.p_thr), _table_ptr(cat.t_thr),
@@ -1900,7 +1931,7 @@ def reduce_statistics(kind: str, inputs: Sequence[xr.DataArray | None], dims: Se
   #  tables, inputs that do not follow the chunk such as the climatology, threshold tables)
   # (input 2 only where it is the SAME array chunk after chunk: the climatology behind a gather table, a threshold field -- an
   #  aligned climatology materialised per chunk is left unaccounted for, and such a chunk is not recorded)
-  replay.keep(dplan, w_buf, *(getattr(cat_args, f) for f in row.keep),
+  replay.keep(dplan, w_buf, *(getattr(cat_args, f, None) for f in row.keep),  # (None: an arm of the row without that table)
               devs[2] if (devs[2] is not None and (gather is not None or thr_field is not None or row.keep2)) else None,
               # (a mask that outlives the chunk: the places whose dry fraction is in range, kind 'seeps')
               devs[3] if (mask is not None and cat and cat.get('mask_da') is mask) else None)

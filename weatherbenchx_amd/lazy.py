@@ -44,6 +44,10 @@ def cat_lanes_per_launch(func: int, masked: bool, skipna: bool) -> int:
 # False (WBX_FUSED_CONTINGENCY=0): thresholded contingency tables (categorical.TruePositives .. behind wrappers.ContinuousToBinary)
 # are materialised and reduced on the host route as before wbx_contingency_partial existed (A/B timing and tests).
 FUSED_CONTINGENCY = os.environ.get('WBX_FUSED_CONTINGENCY', '1') != '0'
+# False (WBX_FUSED_CONTINGENCY_FIELD=0): the same tables at a threshold FIELD (ContinuousToBinary('both', DataArray / Dataset, dim):
+# per-gridpoint thresholds such as a climatological percentile) are binarised and reduced on the host route as before
+# wbx_contingency_field_partial existed (A/B timing and tests).  WBX_FUSED_CONTINGENCY=0 switches the whole family off, fields included.
+FUSED_CONTINGENCY_FIELD = os.environ.get('WBX_FUSED_CONTINGENCY_FIELD', '1') != '0'
 # False (WBX_FUSED_ENS_RPS=0): probabilistic.EnsembleRankedProbabilityScore builds the [K, M, frame] indicator arrays of its two
 # ContinuousToCDF transforms on the host and reduces them as before wbx_ens_rps_partial existed (A/B timing and tests).
 FUSED_ENS_RPS = os.environ.get('WBX_FUSED_ENS_RPS', '1') != '0'
@@ -249,6 +253,18 @@ def _reduce_threshold_blocks(launch, thr, ngroup: int, block: int, **extra):
                                (ngroup * nthr,) + parts[0].shape[1:]))
 
 
+def _reduce_position_blocks(launch, size: int, ngroup: int, block: int, **extra):
+  """_reduce_threshold_blocks for thresholds that lie along a dim of input 2 (a threshold field): a block is named by its POSITIONS
+  along that dim, one launch -- `cat` = {'thr_first', 'nthr', 'size', **extra} -- per block of at most `block` of the `size`
+  thresholds, each block advancing 'thr_first'; the same lanes g * K + k, joined in the same way, ONE launch handed on as it is."""
+  if size <= block:
+    return launch(dict(extra, thr_first=0, nthr=size, size=size))
+  groups = lambda a: a.reshape((ngroup, a.shape[0] // ngroup) + a.shape[1:])
+  return _reduce_in_blocks([dict(extra, thr_first=k0, nthr=min(block, size - k0), size=size) for k0 in range(0, size, block)], launch,
+                           lambda parts: np.concatenate([groups(a) for a in parts], axis=1).reshape(
+                               (ngroup * size,) + parts[0].shape[1:]))
+
+
 def _group_known(p, t, kind: str, pred=lambda key: True) -> bool:
   """A group of kind `kind` of these very objects exists (`pred`: of the rest of its key): an earlier statistic has checked
   their frames."""
@@ -270,7 +286,9 @@ class FusedGroup:
     # 'quantile_dim'} (engine._ivl_operands), growing as statistics join; kind 'seeps': {'dry_threshold', 'table', 'place_dims',
     # 'device_tables', 'host', 'mask_da'} (seeps_statistic); kind 'fss': {'sizes', 'scalar', 'wrap_longitude', 'masks' (one DataArray
     # per size, or None), 'thresholds' (float64 ndarray, or None: binary inputs), 'threshold_dim', 'coord'} (fss_statistic); kind 'brier': {'thresholds', 'values', 'coord', 'threshold_dim', 'denom'} (brier_statistic) or {'quantiles': True, 'thresholds': the levels, 'values', 'coord', 'threshold_dim'} (quantile_error_statistic);
-    # kind 'erpsf': {'bin_dim', 'nthr', 'side_dim', 'right_inclusive', 'host'} (ens_rps_field_statistic)
+    # kind 'erpsf': {'bin_dim', 'nthr', 'side_dim', 'right_inclusive', 'host'} (ens_rps_field_statistic);
+    # kind 'cont' at a threshold field: {'threshold_dim', 'size' (thresholds along it), 'coord' (its labels, or None)}
+    # (contingency_field_statistic)
     self.clim: ClimatologyRef | None = None
     self._clim_key = None
     drop = (ens['member_dim'],) if ens else ((cat['member_dim'],) if cat and cat.get('member_dim') else ())
@@ -329,8 +347,12 @@ class FusedGroup:
     if how == _PER_SIZE:
       return self._reduce_fss(inputs, reduce_dims, w_da, bin_dims, use_mask, skipna)
     # (the fair / inclusive settings of an 'erps' / 'enrg' group and the power of a 'vgrm' group are its own)
-    launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
-                                                  skipna=skipna, ens=self.ens, cat=cat)
+    if self.clim is not None:  # ('cont' at a field: blocks of thresholds of the field, which is input 2 of every launch)
+      launch = lambda cat: _reduce_with_gather(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, func=func,
+                                               mask=mask, skipna=skipna, clim=self.clim, ens=self.ens, cat=cat, may_align=False)
+    else:
+      launch = lambda cat: engine.reduce_statistics(self.kind, inputs, self.dims, self.sizes, reduce_dims, w_da, bin_dims, mask=mask,
+                                                    skipna=skipna, ens=self.ens, cat=cat)
     return launch(self.cat) if how == _PLAIN else how(self, launch, mask, skipna)
 
   def _reduce_cat(self, launch, mask, skipna):
@@ -567,8 +589,12 @@ _LAZY_KINDS = {
     'ens': _LazyKind(None, _GATHER),
     'ens2': _LazyKind(points=lambda g, arr: arr),
     'cat': _LazyKind(reduce=FusedGroup._reduce_cat),  # pylint: disable=protected-access
-    'cont': _LazyKind(reduce=lambda g, launch, mask, skipna: _reduce_threshold_blocks(
-        launch, g.cat['thresholds'], _hip.CONT_CELLS, _hip.CONT_MAX_THRESHOLDS)),
+    # (second arm, a threshold FIELD -- `group.clim`, input 2 of every launch --: blocks of positions along the field's threshold dim)
+    'cont': _LazyKind('optional', lambda g, launch, mask, skipna:
+                      _reduce_position_blocks(launch, int(g.cat['size']), _hip.CONT_CELLS, _hip.CONT_MAX_THRESHOLDS,
+                                              threshold_dim=g.cat['threshold_dim'])
+                      if g.clim is not None else
+                      _reduce_threshold_blocks(launch, g.cat['thresholds'], _hip.CONT_CELLS, _hip.CONT_MAX_THRESHOLDS)),
     'erps': _LazyKind(host=_rebuilt(lambda mv, g, lane: mv.EnsembleRankedProbabilityScore(  # (the indicator arrays of the two
         # ContinuousToCDF transforms and labelled-array arithmetic on them)
         g.cat['p_values'], g.cat['t_values'], g.cat['bin_dim'], '', ensemble_dim=g.ens['member_dim'], skipna_ensemble=False,
@@ -906,6 +932,48 @@ class LazyContingency(xr.LazyPickleMixin, xr.DataArray):
     return np.dtype(np.float32)
 
 
+class LazyContingencyField(LazyContingency):
+  """LazyContingency at a threshold FIELD: the thresholds of `ContinuousToBinary('both', DataArray / Dataset, dim)` vary with the
+  point (the local climatological 95th percentile, a per-station warning level).  The four cells of one (p, t, field) share a
+  FusedGroup of kind 'cont' whose `clim` is the field, so the Aggregator gets all of them from one launch per block of
+  _hip.CONT_MAX_THRESHOLDS thresholds (wbx_contingency_field_partial).  Reading `.data` is the unfused route on the host, as for
+  lists.  The threshold dim is labelled where the field labels it."""
+
+  def __init__(self, group: FusedGroup, cell: int, threshold_dim: str, name=None):
+    self._data = None
+    self._dims = tuple(group.dims) + (threshold_dim,)
+    self.name = name
+    self.attrs = {}
+    self._coords = dict(group.coords)
+    if group.cat['coord'] is not None:
+      self._coords[threshold_dim] = ((threshold_dim,), np.asarray(group.cat['coord']))
+    self._group = group
+    self._cell = int(cell)
+    self._threshold_dim = threshold_dim
+
+  @property
+  def nthr(self) -> int:
+    return int(self._group.cat['size'])
+
+  @staticmethod
+  def launchable() -> bool:
+    return (FUSED_CONTINGENCY and FUSED_CONTINGENCY_FIELD
+            and engine.contingency_field_available(_hip.default_context()))
+
+  @property
+  def data(self):
+    if self._data is None:
+      from weatherbenchx_amd.metrics import categorical, wrappers  # pylint: disable=g-import-not-at-top
+      grp = self._group
+      field = grp.clim.aligned_view() if grp.clim.positions else grp.clim.source
+      pb = wrappers.binarize_thresholds(grp.p, field, self._threshold_dim)
+      tb = wrappers.binarize_thresholds(grp.t, field, self._threshold_dim)
+      predicted, observed = ((True, True), (True, False), (False, True), (False, False))[self._cell]
+      out = categorical._indicator(pb, tb, predicted, observed)  # pylint: disable=protected-access
+      self._data = out.transpose(*self._dims).data
+    return self._data
+
+
 class LazyBrier(xr.LazyPickleMixin, xr.DataArray):
   """Error, AbsoluteError or SquaredError of (the fraction of members over a threshold, or the indicator of a deterministic
   prediction) against (the target is over that threshold) along a new trailing `threshold_dim`: what these statistics are behind
@@ -1203,6 +1271,31 @@ def contingency_statistic(cell: int, p, t, threshold_dim: str, thresholds) -> xr
   cat = {'thresholds': thr, 'values': values, 'coord': np.asarray(values), 'threshold_dim': threshold_dim}
   grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
   return LazyContingency(grp, cell, threshold_dim, name=p.name)
+
+
+def contingency_field_statistic(cell: int, p, t, threshold_dim: str, ref: ClimatologyRef, *, clim_key=None) -> xr.DataArray:
+  """Cell `cell` (0..3: TP, FP, FN, TN) of the 2x2 table of (p > thr_k, t > thr_k) at the threshold field behind `ref` (its source
+  carries `threshold_dim`; the kernel addresses that dim itself) as a LazyContingencyField on a FusedGroup of kind 'cont'
+  (wbx_contingency_field_partial).  The (p, t) objects, the field (`clim_key`: its identity and state) and the dim key the group, so
+  the four cells of a (p, t, field) meet in one group and one launch per block of thresholds.  Raises ValueError where the field
+  does not broadcast against the frame: the caller keeps the host route."""
+  p, t = xr.as_dataarray(p), xr.as_dataarray(t)
+  if threshold_dim in p.dims or threshold_dim in t.dims:
+    raise ValueError(f'{threshold_dim!r} is already a dimension of the inputs')
+  source = ref.source
+  if threshold_dim not in source.dims:
+    raise ValueError(f'the threshold field has dims {source.dims}')
+  ckey = ('contf', clim_key, threshold_dim)
+  if not _group_known(p, t, 'cont', lambda k: k[4] == ckey):
+    p, t = _aligned(p, t)
+  if source.sizes[threshold_dim] > 1 and payload_layout(source).stride(threshold_dim) == 0:
+    raise ValueError(f'the threshold dim {threshold_dim!r} of the field is a broadcast view (stride 0)')  # (engine._contf_operands)
+  coord = np.asarray(source.coords[threshold_dim].values) if threshold_dim in source.coords else None
+  cat = {'threshold_dim': threshold_dim, 'size': int(source.sizes[threshold_dim]), 'coord': coord}
+  grp = _group_for('cont', p, t, clim_key=ckey, cat=cat)
+  if not grp.attach_climatology(ref, ckey, own_dims=(threshold_dim,)):
+    raise ValueError(f'threshold field dims {ref.aligned_dims()} do not broadcast against the statistic dims {grp.dims}')
+  return LazyContingencyField(grp, cell, threshold_dim, name=p.name)
 
 
 EPC_COUNT_DIM = '__member_count__'  # the dim of the column of counts c = 0..M that the slot table is derived from

@@ -50,7 +50,8 @@ class _Indicator(base.PerVariableStatistic):
   def compute_with_transform(self, transform, predictions, targets):
     """This cell behind `wrappers.ContinuousToBinary('both', [numbers], dim)` as lazy statistics on the continuous inputs (one
     fused launch for the four cells of a variable, lazy.contingency_statistic), or None when the combination is not the plain one:
-    the caller then transforms and computes as usual."""
+    the caller then transforms and computes as usual.  Thresholds that are a DataArray / Dataset -- a threshold per grid point --
+    go through `_at_threshold_field`."""
     if not lazy.FUSED_CONTINGENCY or type(self) not in _CELL_INDEX or type(transform) is not wrappers.ContinuousToBinary:  # pylint: disable=unidiomatic-typecheck
       return None
     if transform.which != 'both':
@@ -58,6 +59,8 @@ class _Indicator(base.PerVariableStatistic):
     values = wrappers.plain_thresholds(transform._threshold_value)  # pylint: disable=protected-access
     dim = transform._threshold_dim  # pylint: disable=protected-access
     if values is None:
+      if isinstance(transform._threshold_value, (xr.DataArray, xr.Dataset)):  # pylint: disable=protected-access
+        return self._at_threshold_field(transform._threshold_value, dim, predictions, targets)  # pylint: disable=protected-access
       return None
     pairs = {}
     for name in predictions.keys():
@@ -69,6 +72,46 @@ class _Indicator(base.PerVariableStatistic):
         return None
       pairs[name] = (p, t)
     return {name: lazy.contingency_statistic(_CELL_INDEX[type(self)], p, t, dim, values) for name, (p, t) in pairs.items()}
+
+  def _at_threshold_field(self, thresholds, dim, predictions, targets):
+    """This cell at a threshold field (`thresholds`: the DataArray, or the Dataset that holds one per variable) as lazy statistics
+    on the continuous inputs (one launch of wbx_contingency_field_partial per block of thresholds for the four cells of a variable,
+    lazy.contingency_field_statistic), or None where `contingency_field_route` says host for a variable, the field is host-resident
+    behind a slab pool, the switch is off, there is no device or no entry point.  Never raises: where the host route would -- a
+    Dataset without the variable, a field without the threshold dim --, the host route does."""
+    if not lazy.FUSED_CONTINGENCY_FIELD:
+      return None
+    from weatherbenchx_amd import climatology_cache  # pylint: disable=g-import-not-at-top
+    names = [name for name in predictions.keys() if name in targets.keys()]
+    if isinstance(thresholds, xr.Dataset):
+      # the host route looks the field up by the name each array carries ITSELF and asserts that it is there: asked before
+      # base._named gives a nameless array its variable's name
+      for name in names:
+        own = {getattr(predictions[name], 'name', None), getattr(targets[name], 'name', None)}
+        if own != {name} or name not in thresholds.data_vars:
+          return None
+    triples = {}
+    for name in names:
+      p, t = base._named(predictions[name], name), base._named(targets[name], name)  # pylint: disable=protected-access
+      field = thresholds[name] if isinstance(thresholds, xr.Dataset) else thresholds
+      if contingency_field_route(p, t, field, dim)[0] != 'fused' or climatology_cache.cache_for(field) is not None:
+        return None
+      triples[name] = (p, t, field)
+    try:
+      ctx = _hip.default_context()
+    except _hip.WbxUnavailableError:  # no device or no library: nothing to launch on (the host route says so where it needs one)
+      return None
+    if not engine.contingency_field_available(ctx):
+      return None
+    out = {}
+    for name, (p, t, field) in triples.items():
+      try:
+        ref = lazy.ClimatologyRef(field, (), {})  # (nothing is selected along a time dim: the field as it is, no gather table)
+        out[name] = lazy.contingency_field_statistic(_CELL_INDEX[type(self)], p, t, dim, ref,
+                                                     clim_key=(id(field), field.__dict__.get('_mutations', 0)))
+      except (ValueError, lazy._NeedsAlignment):  # pylint: disable=protected-access  (a frame the field does not broadcast against)
+        return None
+    return out
 
   def compute_with_chain(self, transforms, predictions, targets):
     """This cell behind the documented chain for ensembles as probability forecasts, `transforms` = (ContinuousToBinary('both',
@@ -127,6 +170,42 @@ class _Indicator(base.PerVariableStatistic):
       out[name] = lazy.ens_prob_contingency_statistic(_CELL_INDEX[type(self)], p, t, e, event_dim, values, slot_dim, table[1], table[0],
                                                       (outer, mean, inner), inner_key=inner_key)
     return out
+
+
+def contingency_field_route(predictions, targets, field, threshold_dim: str):
+  """Where a cell of the contingency table at the threshold field `field` (the variable's DataArray behind
+  ContinuousToBinary('both', field, threshold_dim)) goes, decided from labels, dims and dtypes alone (no device, no look at the
+  values): ('fused', None) -- one launch of wbx_contingency_field_partial per block of thresholds, the field read in place -- or
+  ('host', the reason).  Fused needs: `threshold_dim` on the field and on neither input; at least one other dim on the field (a
+  labelled array with the threshold dim alone is a list: the host route); every other dim of the field a dim of both inputs, of
+  equal length and with equal labels in equal order (labels that differ: xarray joins on their intersection) or unlabelled on all
+  three; target dims among the prediction dims; float32 / float64 throughout; no coordinates on the field beyond those of its own
+  dims (they would join the result's)."""
+  host = lambda why: ('host', why)
+  if not isinstance(field, xr.DataArray):
+    return host('thresholds that are not a field')
+  p, t = xr.as_dataarray(predictions), xr.as_dataarray(targets)
+  if threshold_dim not in field.dims:
+    return host('a field without the threshold dim')  # (the host route's assertion)
+  others = [d for d in field.dims if d != threshold_dim]
+  if not others:
+    return host('a labelled list: the threshold dim alone')
+  if threshold_dim in p.dims or threshold_dim in t.dims or not set(t.dims) <= set(p.dims):
+    return host('the frames of predictions and targets')
+  floats = ('float32', 'float64')
+  if any(str(a.dtype).replace('torch.', '') not in floats for a in (p, t, field)):
+    return host('dtypes other than float32 / float64')
+  for d in others:
+    for x in (p, t):
+      if d not in x.dims or x.sizes[d] != field.sizes[d]:
+        return host(f'the field dim {d!r} is not a dim of both inputs, or of another length')
+      if (d in field.coords) != (d in x.coords):
+        return host(f'the dim {d!r} is labelled on one side only')
+      if d in field.coords and not xr._values_equal(field._coords[d][1], x._coords[d][1]):  # pylint: disable=protected-access
+        return host(f'labels of {d!r} that differ')  # (the host route joins on the labels they share)
+  if set(field.coords) - set(field.dims):
+    return host('coordinates of the field beyond those of its own dims')
+  return 'fused', None
 
 
 class TruePositives(_Indicator):
